@@ -1,9 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark: DiLoCo outer step, device-resident, GB/s of parameters reduced.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--tree t125]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--tree t125] [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times
+the K steps, writes the last timed step's outputs if --dump-outputs DIR is given (DIR/theta.npy,
+grad.npy, momentum.npy, inner.npy: what a caller of the four calls holds after that step, float32,
+a fixed seeded sample of each when the tree is larger than the dump's budget; the inputs are
+counter-based, so two builds run with the same arguments can be compared output for output) and
+prints the line. --full adds everything else the benchmark measures or checks: the cold pass, the
+CPU baseline, the parity self-checks, the side legs (other trees, wires, placements, exchanges),
+the exchange's own roofline at N > 1 and the detail file.
 
 One step = one outer step of src/train.py:261-269 over the whole synthetic tree on every rank,
 made through the reference's own calls -- compute_pseudo_gradient -> TrainingComm.sync_gradients
@@ -19,10 +28,11 @@ Same tree per rank at every N (weak scaling). value = 4 * params / t_step (SURVE
 params reduced": the bytes of ONE parameter tree reduced per DP step, max time over ranks);
 N * 4 * params / t_step is "value_aggregate".
 
-Rank 0 prints ONE compact JSON line (<= 4 KB: the headline, its roofline kernel, the CPU
-baseline, one-number summaries of the side legs, parity ok/err, the exchange efficiency at
-N > 1) and writes every leg's full record to a side file (--detail, default
-gpurun_out/bench_detail_n<N>.json). A watchdog bounds the run (--deadline): the line is printed
+Rank 0 prints ONE compact JSON line (<= 4 KB: the headline, its roofline kernel and, with
+--full, the CPU baseline, one-number summaries of the side legs, parity ok/err, the exchange
+efficiency at N > 1) and, with --full or --detail, writes every leg's full record to a side
+file (--detail PATH; with --full alone bench_detail_n<N>.json in the run-output folder beside
+this file). A watchdog bounds the run (--deadline): the line is printed
 whatever a side leg does; a heartbeat on stderr names the running leg every 20 s. A/B-only
 measurements (copy / mix ceilings, the two-kernel and wire-less steps, RCCL setting variants)
 live in tools/bench_ab.py.
@@ -239,7 +249,8 @@ def _dropin_objects(spec, dev, rank, wire, bucket_elems, exchange, placement=Non
 
 
 def run_dropin(spec, dev, ws, rank, steps, warmup, wire="f32", bucket_elems=None,
-               exchange=None, cold=False, synced=False, placement=None):
+               exchange=None, cold=False, synced=False, placement=None, exchange_probe=True,
+               dump=None):
     """The outer step through the reference's call surface, src/train.py:263-269, on the outer
     model get_outer_model returns (placement None: the default, the reference's CPU outer
     model stepped on its HBM twin; "device": the outer model in HBM; exchange None: that
@@ -249,7 +260,9 @@ def run_dropin(spec, dev, ws, rank, steps, warmup, wire="f32", bucket_elems=None
     around its outer step (src/train.py:244), so the calls' host time is exposed; each step is
     timed on its own and the value is the median step's (one host stall on a shared box moved a
     10-step mean from 0.68 to 5.3 ms; the mean stays in the record). cold (N = 1): then K more
-    steps, each after an Infinity-Cache scrub outside the events."""
+    steps, each after an Infinity-Cache scrub outside the events. exchange_probe (N > 1): the
+    exchange's collectives timed in a pass of their own for the roofline record. dump: a
+    folder for the last timed step's outputs (dump_outputs), written before any further step."""
     from diloco_amd.utils import compute_pseudo_gradient, sync_inner_model
 
     inner, outer, opt, comm = _dropin_objects(spec, dev, rank, wire, bucket_elems, exchange,
@@ -288,6 +301,11 @@ def run_dropin(spec, dev, ws, rank, steps, warmup, wire="f32", bucket_elems=None
     mean_ms = dt * 1e3
     if synced:  # every step ended with a synchronize: its own wall time is the step's
         dt = _max_over_ranks(float(np.median(per)), dev, ws)
+    if dump:  # what the caller of the four calls holds after the last timed step
+        outs = list(outer.parameters())
+        dump_outputs(dump, {"theta": [p.data for p in outs], "grad": [p.grad for p in outs],
+                            "momentum": [opt.state[p]["momentum_buffer"] for p in outs],
+                            "inner": [p.data for p in inner.parameters()]}, write=rank == 0)
     P = spec.total()
     mm = outer._diloco_mirror
     m = getattr(mm, "dev", mm)  # the lazy host placement steps on its HBM twin
@@ -323,7 +341,7 @@ def run_dropin(spec, dev, ws, rank, steps, warmup, wire="f32", bucket_elems=None
             res["cold"] = {"step_ms": round(c_ms, 5), "value": 4.0 * P / (c_ms * 1e-3) / 1e9,
                            "note": "Infinity Cache scrubbed before each step (512 MiB copy "
                                    "outside the events); the four calls' event span"}
-    else:
+    elif exchange_probe:
         res["roofline"] = exchange_roofline(m, ws, dev, steps, comm.dp.dp_group(dev))
     mm.close()
     del outer, opt, inner, m, mm
@@ -339,6 +357,43 @@ def _spread(xs):
     return {"median": round(float(np.median(a)), 4), "mean": round(float(a.mean()), 4),
             "p90": round(float(a[int(0.9 * (len(a) - 1))]), 4), "max": round(float(a[-1]), 4),
             "slowest": [round(float(x), 3) for x in a[-5:][::-1]]}
+
+
+DUMP_MAX_BYTES = 48 * 10 ** 6  # array data --dump-outputs writes in all (the files: <= 64 MB)
+DUMP_SEED = 20240607  # of the sample kept of an array larger than its share of that budget
+
+
+def dump_indices(total, n_arrays):
+    """The flat element indices --dump-outputs keeps of an array of `total` elements when
+    n_arrays float32 arrays share DUMP_MAX_BYTES: None (all of them) if they fit, else a fixed
+    seeded sample (sorted, drawn with replacement: the same for every run and every build)."""
+    keep = DUMP_MAX_BYTES // (4 * n_arrays)
+    if total <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, size=keep, dtype=np.int64))
+
+
+def dump_outputs(path, arrays, write=True):
+    """--dump-outputs: arrays = {name: the tensors of one output, in parameter order} ->
+    path/<name>.npy, float32, the flat concatenation of the tensors or dump_indices' sample of
+    it. Every rank reads (under a sharded exchange a read is a collective); `write` says
+    whether this rank writes the files."""
+    for name, ts in arrays.items():
+        ts = [t.detach().reshape(-1) for t in ts]
+        idx = dump_indices(sum(t.numel() for t in ts), len(arrays))
+        if idx is None:
+            parts = [t.float().cpu() for t in ts]
+        else:
+            ends = np.cumsum([t.numel() for t in ts])
+            cuts = np.searchsorted(idx, ends)
+            parts = []
+            for t, lo, hi, end in zip(ts, np.concatenate(([0], cuts[:-1])), cuts, ends):
+                local = torch.from_numpy(idx[lo:hi] - (end - t.numel())).to(t.device)
+                parts.append(t[local].float().cpu())
+        out = torch.cat(parts).numpy()
+        if write:
+            os.makedirs(path, exist_ok=True)
+            np.save(os.path.join(path, name + ".npy"), out)
 
 
 def exchange_roofline(m, ws, dev, steps, group):
@@ -1193,10 +1248,10 @@ def assemble_line(meta, head, cpu, legs, parity, exch=None, extra=None):
     exchange efficiencies at N > 1. Strings that could grow are capped; if the line is still
     too long, side legs are dropped from the end (their records stay in the detail file)."""
     ws = meta["n_gpus"]
-    roof = dict(head["roofline"])
+    roof = head.get("roofline")  # None: a plain run at N > 1 (the exchange's probe is --full's)
     keep = ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "bytes_per_launch",
             "avg_ms")
-    roof = {k: roof.get(k) for k in keep}
+    roof = {k: roof.get(k) for k in keep} if isinstance(roof, dict) else None
     cold = head.get("cold")
     cb = None
     if isinstance(cpu, dict) and "value" in cpu:
@@ -1327,12 +1382,20 @@ def main():
     ap.add_argument("--tree", default="t125")
     ap.add_argument("--bucket-mb", type=int, default=256)
     ap.add_argument("--extra-tree", default="t1.3b", help="second tree measured beside (or 'none')")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the cold pass, the CPU baseline, the parity "
+                         "self-checks, every side leg, the exchange's roofline at N > 1 and the "
+                         "detail file (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (theta, grad, "
+                         "momentum, inner) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-xgmi", action="store_true",
                     help="skip the isolated peer-access legs at N > 1")
     ap.add_argument("--only-headline", action="store_true",
-                    help="headline only, no cold pass (rocprofv3 runs of the same kernel)")
+                    help="with --full: the headline only (at N > 1 with the exchange's roofline), "
+                         "no cold pass (rocprofv3 runs of the same kernel)")
     ap.add_argument("--no-b2b", action="store_true", help=argparse.SUPPRESS)  # kept: old scripts
     ap.add_argument("--detail", default=None,
                     help="side file of full records (default gpurun_out/bench_detail_n<N>.json)")
@@ -1380,6 +1443,9 @@ def main():
 
     ws0 = int(os.environ.get("WORLD_SIZE", "1"))
     detail = a.detail or os.path.join(HERE, "gpurun_out", f"bench_detail_n{ws0}.json")
+    full = a.full and not a.only_headline
+    if not (a.full or a.detail):
+        detail = None  # a plain run writes no side file unless asked to
     em = _Emitter(int(os.environ.get("RANK", "0")), a.deadline, detail)
     soft = 0.7 * a.deadline
     ws, rank, dev = setup_dist(a.gpus)
@@ -1394,7 +1460,8 @@ def main():
     log(f"rank {rank}/{ws} tree {spec.name} ({spec.total()} params)")
 
     # the headline: the reference's four calls on the fused device outer model
-    head = run_dropin(spec, dev, ws, rank, a.steps, a.warmup, cold=ws == 1 and not a.only_headline)
+    head = run_dropin(spec, dev, ws, rank, a.steps, a.warmup, cold=ws == 1 and full,
+                      exchange_probe=a.full, dump=a.dump_outputs)
     workload = (f"DiLoCo outer step, {spec.name} tree per rank, through the reference's calls "
                 "(src/train.py:263-269) on get_outer_model's default (CPU) outer model, stepped "
                 "on its HBM twin: "
@@ -1432,7 +1499,7 @@ def main():
         return r
 
     # the CPU baseline first after the headline (the line needs it; the side legs do not)
-    if not a.no_cpu_baseline and not a.only_headline:
+    if full and not a.no_cpu_baseline:
         em.running = "cpu_baseline"
         if ws == 1:
             cpu = _guard(cpu_baseline, spec)
@@ -1450,13 +1517,13 @@ def main():
     # then the parity the line must carry at any N, ahead of every side leg (a slow side leg
     # can no longer cost the line its parity): the f32 average against torch, and at N > 1
     # the headline path's exchanges behind the reference's calls against each other
-    if not a.no_parity and not a.only_headline:
+    if full and not a.no_parity:
         leg("f32", parity_f32, dev, ws, rank, into=parity, always=True)
         if ws > 1:
             leg("dropin_exchanges", parity_dropin_exchanges, dev, ws, rank, into=parity,
                 always=True)
 
-    if not a.only_headline:
+    if full:
         if ws == 1:
             leg(f"{spec.name}_engine", run_engine, spec, dev, ws, rank, a.steps, a.warmup,
                 torch.float32, cap, True, None, "rccl", True)

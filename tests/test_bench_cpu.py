@@ -205,6 +205,49 @@ def test_line_drops_side_legs_rather_than_grow():
     assert line["legs_dropped_from_line"] > 0 and line["value"] == 830.0
 
 
+def test_plain_line_without_side_legs():
+    """A plain run's line (no --full: no CPU baseline, legs, parity, cold pass; at N > 1 no
+    exchange probe, so no roofline record) still carries the fields the driver reads."""
+    bench, meta, head, _, _, _, _ = _full_run_records(8)
+    del head["cold"], head["roofline"]
+    d = json.loads(json.dumps(bench.assemble_line(meta, head, None, {}, {}, None)))
+    assert d["metric"] == bench.METRIC and d["value"] == 830.0 and d["unit"] == "GB/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["ms_per_step"] == 0.6
+    assert d["steps"] == 50 and d["warmup"] == 3
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["value_cold"] is None
+    assert d["legs"] == {} and d["parity"] == {}
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: arrays that fit the budget are written whole (float32, the tensors'
+    flat concatenation); larger ones as the same seeded sample on every call, the files
+    together within the budget."""
+    import sys as _sys
+
+    import numpy as np
+    import torch
+
+    _sys.path.insert(0, REPO)
+    import bench
+
+    ts = {"a": [torch.arange(5.0).view(5, 1), torch.arange(5.0, 12.0)],
+          "b": [torch.arange(12.0, dtype=torch.float64) * 2]}
+    bench.dump_outputs(str(tmp_path / "w"), ts)
+    a, b = np.load(tmp_path / "w" / "a.npy"), np.load(tmp_path / "w" / "b.npy")
+    assert a.dtype == np.float32 and b.dtype == np.float32
+    assert a.tolist() == list(range(12)) and b.tolist() == [2 * i for i in range(12)]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 4 * 6)  # 6 elements for each of 2 arrays
+    idx = bench.dump_indices(12, 2)
+    assert len(idx) == 6 and (np.diff(idx) >= 0).all() and 0 <= idx[0] and idx[-1] < 12
+    assert (idx == bench.dump_indices(12, 2)).all()
+    bench.dump_outputs(str(tmp_path / "s"), ts)
+    bench.dump_outputs(str(tmp_path / "r"), ts, write=False)
+    assert not (tmp_path / "r").exists()
+    a, b = np.load(tmp_path / "s" / "a.npy"), np.load(tmp_path / "s" / "b.npy")
+    assert a.tolist() == idx.tolist() and b.tolist() == (2 * idx).tolist()
+    assert a.nbytes + b.nbytes <= bench.DUMP_MAX_BYTES
+
+
 def test_dropin_hbm_bytes_per_param():
     """The drop-in step's kernel bytes per parameter: one pass 28 at one
     peer; sharded 12 (pack) + 20/n (shard SGD) + 8 (scatter); replicated 12 + 24."""

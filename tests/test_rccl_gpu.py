@@ -477,14 +477,27 @@ def test_rccl_single_rank_device_mirror_exchanges():
 
 
 def _ports():
-    """A port p with p + 1 free too (World puts its TCPStore on MASTER_PORT + 1)."""
-    for _ in range(50):
-        p = _free_port()
-        with socket.socket() as s:
-            try:
-                s.bind(("127.0.0.1", p + 1))
-            except OSError:
-                continue
+    """A port p with p + 1 free too (World puts its TCPStore on MASTER_PORT + 1, on every local
+    address). Both are taken from below the kernel's ephemeral range: p + 1 cannot be held
+    while the worker starts, and inside that range any outgoing connection made on the machine
+    in those seconds may be given it (the store then fails with EADDRINUSE)."""
+    import random
+
+    try:
+        with open("/proc/sys/net/ipv4/ip_local_port_range") as f:
+            low = int(f.read().split()[0])
+    except (OSError, ValueError, IndexError):
+        low = 32768
+    top = max(min(low, 32768) - 2, 12002)
+    rng = random.Random(os.getpid() ^ int.from_bytes(os.urandom(4), "little"))
+    for _ in range(200):
+        p = rng.randrange(top - 10000, top)
+        try:
+            with socket.socket() as a, socket.socket() as b:
+                a.bind(("", p))
+                b.bind(("", p + 1))
+        except OSError:
+            continue
         return p
     raise RuntimeError("no free port pair")
 

@@ -7,6 +7,7 @@ cd $R && mkdir -p gpurun_out/n4probe
 for np in 2 4; do
   DILOCO_BENCH_BACKEND=gloo timeout -k 10 240 python -m torch.distributed.run \
     --nnodes=1 --nproc-per-node $np --master-addr 127.0.0.1 --master-port 2952$np bench.py --gpus $np \
+    --full \
     --only-headline --steps ${STEPS:-6} --warmup 1 --detail gpurun_out/n4probe/d_$np.json \
     > gpurun_out/n4probe/l_$np.json 2> gpurun_out/n4probe/e_$np.txt \
     || { echo "n=$np failed"; tail -20 gpurun_out/n4probe/e_$np.txt; exit 1; }

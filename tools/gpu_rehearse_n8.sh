@@ -8,6 +8,7 @@ NP=${NP:-8}
 t0=$(date +%s)
 DILOCO_BENCH_BACKEND=gloo timeout -k 10 ${LIMIT:-600} python -m torch.distributed.run --nnodes=1 --nproc-per-node $NP \
   --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus $NP --detail gpurun_out/bench_detail_n${NP}_gloo_$TAG.json $ARGS \
+  --full \
   > gpurun_out/bench_n${NP}_gloo_$TAG.json 2> gpurun_out/bench_n${NP}_gloo_$TAG.err || { echo n$NP rehearsal failed; tail -40 gpurun_out/bench_n${NP}_gloo_$TAG.err; exit 1; }
 echo "wall $(( $(date +%s) - t0 )) s"
 cat gpurun_out/bench_n${NP}_gloo_$TAG.json

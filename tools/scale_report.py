@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarise bench.py's compact lines from a scaling run (one JSON line per N: the driver's
+"""Summarise `bench.py --full`'s compact lines from a scaling run (one JSON line per N: the driver's
 SCALE_rNN.json, or several bench outputs) against the N > 1 model of DESIGN.md §4: the headline
 (the reference's calls on the sharded exchange), its exchange roofline, the exchange efficiency
 per tree (the step's bus rate over RCCL's own all_reduce of the same bytes), every leg's GB/s and
