@@ -551,6 +551,47 @@ DL_API int dl_delta_pack_sgd(dl_tree_t t, int32_t b, int32_t inner_slot, float* 
   return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_pack_sgd") : hip_fail(e, "dl_delta_pack_sgd");
 }
 
+// The AdamW outer step (dl_adamw.hip). Like the SGD kernels, nothing re-reads what they write
+// next: non-temporal loads and stores.
+DL_API int dl_unpack_adamw(dl_tree_t t, int32_t b, const void* wire, int32_t wire_dtype,
+                           int32_t divisor, float* outer, float* exp_avg, float* exp_avg_sq,
+                           float decay, float w1, float beta2, float w2, float neg_step_size,
+                           float bc2_sqrt, float eps, int32_t inner_slot, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_adamw", kAutoUnpackSgd));
+  DL_TRY(check_packed(wire, "dl_unpack_adamw", "wire"));
+  DL_TRY(check_dtype(wire_dtype, "dl_unpack_adamw"));
+  DL_TRY(check_packed(outer, "dl_unpack_adamw", "outer"));
+  DL_TRY(check_packed(exp_avg, "dl_unpack_adamw", "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, "dl_unpack_adamw", "exp_avg_sq"));
+  DL_TRY(check_slot(t, inner_slot, "dl_unpack_adamw", true));
+  if (divisor < 1) return fail(DL_E_ARG, "dl_unpack_adamw: divisor %d", divisor);
+  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_adamw"));
+  hipError_t e = dl::launch_unpack_adamw(L, wire, wire_dtype, divisor, outer, exp_avg, exp_avg_sq,
+                                         a, inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_adamw") : hip_fail(e, "dl_unpack_adamw");
+}
+
+DL_API int dl_delta_pack_adamw(dl_tree_t t, int32_t b, int32_t inner_slot, float* outer,
+                               void* wire, int32_t wire_dtype, float* exp_avg, float* exp_avg_sq,
+                               float decay, float w1, float beta2, float w2, float neg_step_size,
+                               float bc2_sqrt, float eps, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_delta_pack_adamw", kAutoUnpackSgd));
+  DL_TRY(check_slot(t, inner_slot, "dl_delta_pack_adamw"));
+  DL_TRY(check_packed(outer, "dl_delta_pack_adamw", "outer"));
+  DL_TRY(check_packed(wire, "dl_delta_pack_adamw", "wire"));
+  DL_TRY(check_dtype(wire_dtype, "dl_delta_pack_adamw"));
+  DL_TRY(check_packed(exp_avg, "dl_delta_pack_adamw", "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, "dl_delta_pack_adamw", "exp_avg_sq"));
+  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_delta_pack_adamw"));
+  hipError_t e = dl::launch_delta_pack_adamw(L, inner_slot, outer, wire, wire_dtype, exp_avg,
+                                             exp_avg_sq, a);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_pack_adamw") : hip_fail(e, "dl_delta_pack_adamw");
+}
+
 // a2 -> (one peer: the exchange is the identity, src/comm.py:118-119) -> a3-a5, cache-blocked:
 // the tree is walked in tiles of tile_chunks chunks and each tile runs dl_delta_pack then
 // dl_unpack_sgd, so the wire and θ bytes the pack just touched are re-read by the unpack from

@@ -1,5 +1,5 @@
 // Device-side building blocks shared by the kernel translation units (dl_kernels.hip,
-// dl_q8.hip): streaming memory ops, element conversions, the segment walker and its launcher.
+// dl_q8.hip, dl_adamw.hip): streaming memory ops, element conversions, the segment walker and its launcher.
 #pragma once
 #include <type_traits>
 
@@ -206,6 +206,18 @@ __device__ __forceinline__ void sgd1(float g, float& buf, float& th, const SgdAr
     const float u = a.nesterov ? __builtin_fmaf(buf, a.momentum, g) : buf;
     th = __builtin_fmaf(u, a.neg_lr, th);
   }
+}
+
+// One element of torch's _single_tensor_adamw (dl_adamw.hip has the formula): contract off, so
+// every operation but the two explicit fmas rounds on its own; sqrt and both divisions are
+// correctly rounded (the Makefile's flags).
+__device__ __forceinline__ void adam1(float g, float& m, float& v, float& th, const AdamArgs& a) {
+  th = th * a.decay;
+  m = __builtin_fmaf(a.w1, g - m, m);
+  v = v * a.beta2;
+  v = __builtin_fmaf(a.w2 * g, g, v);
+  const float den = __builtin_sqrtf(v) / a.bs + a.eps;
+  th = th + (a.nss * m) / den;
 }
 
 template <class Body, bool NTL, int NTS>

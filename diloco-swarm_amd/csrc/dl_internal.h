@@ -31,6 +31,18 @@ struct SgdArgs {
   int32_t first;   // momentum buffer not yet created (torch: buf = clone(grad))
 };
 
+// AdamW's per-step scalars, computed by the host in doubles as torch computes them and narrowed
+// to fp32 once (include/diloco_hip.h, dl_unpack_adamw)
+struct AdamArgs {
+  float decay;  // 1 - lr*wd
+  float w1;     // 1 - beta1
+  float beta2;
+  float w2;     // 1 - beta2
+  float nss;    // -(lr / (1 - beta1^t))
+  float bs;     // sqrt(1 - beta2^t)
+  float eps;
+};
+
 struct Launch {
   const Chunk* chunks;  // device chunk table
   int32_t c0, c1;       // chunk range
@@ -83,6 +95,10 @@ hipError_t launch_unpack_sgd_q8(const Launch& L, const uint8_t* slots, float* ou
                                 SgdArgs a, int inner_slot);
 hipError_t launch_q8_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,
                             uint8_t* out, hipStream_t s);
+hipError_t launch_unpack_adamw(const Launch& L, const void* wire, int wire_dtype, int divisor,
+                               float* outer, float* m1, float* m2, AdamArgs a, int inner_slot);
+hipError_t launch_delta_pack_adamw(const Launch& L, int inner_slot, float* outer, void* wire,
+                                   int wire_dtype, float* m1, float* m2, AdamArgs a);
 hipError_t launch_gather(const Launch& L, int src_slot, void* packed, int dtype);
 hipError_t launch_scatter(const Launch& L, const float* packed, int dst_slot);
 hipError_t launch_serialize_f64(const double* src, int64_t numel, float m0, float m1, double* out,

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get(
 )
 
 # constants mirrored from include/diloco_hip.h
-ABI_VERSION = 2
+ABI_VERSION = 3
 ALIGN_ELEMS = 64
 CHUNK_ELEMS = 4096
 ALL_BUCKETS = -1
@@ -62,6 +62,16 @@ SIGNATURES = {
     "dl_delta_sgd": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _vp]),
     "dl_delta_pack_sgd": (
         ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _f32, _f32, _i32, _i32, _vp],
+    ),
+    "dl_unpack_adamw": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
+         _i32, _vp],
+    ),
+    "dl_delta_pack_adamw": (
+        ctypes.c_int,
+        [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
+         _vp],
     ),
     "dl_pack_sgd_tiled": (
         ctypes.c_int,

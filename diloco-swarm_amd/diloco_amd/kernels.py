@@ -29,6 +29,19 @@ def wire_code(dtype: torch.dtype) -> int:
         raise TypeError(f"unsupported packed dtype {dtype} (float32 or bfloat16)") from None
 
 
+def adamw_scalars(lr: float, beta1: float, beta2: float, weight_decay: float, eps: float,
+                  step: float) -> tuple:
+    """The seven per-step scalars of dl_unpack_adamw / dl_delta_pack_adamw (decay, w1, beta2,
+    w2, neg_step_size, bc2_sqrt, eps) in Python doubles, each expression written as torch's
+    _single_tensor_adamw writes it; `step` is the count after this step. The C-ABI call narrows
+    each to fp32 once, as torch does when the Python scalar meets the fp32 tensor."""
+    bias_correction1 = 1 - beta1 ** step
+    bias_correction2 = 1 - beta2 ** step
+    step_size = lr / bias_correction1
+    return (1 - lr * weight_decay, 1 - beta1, beta2, 1 - beta2, -step_size,
+            bias_correction2 ** 0.5, eps)
+
+
 def _s(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
@@ -82,6 +95,21 @@ class HipKernels:
         _lib.call("dl_delta_pack_sgd", tree.handle, bucket, inner_slot, theta.data_ptr(),
                   wire.data_ptr(), wire_code(wire.dtype), _ptr(mom), float(lr), float(momentum),
                   int(nesterov), int(first), _s(theta))
+
+    def unpack_adamw(self, tree, bucket, wire, divisor, theta, exp_avg, exp_avg_sq, scalars,
+                     inner_slot) -> None:
+        """N > 1: the summed wire / divisor, then one AdamW step on θ, exp_avg, exp_avg_sq
+        (and the inner params); scalars from adamw_scalars."""
+        _lib.call("dl_unpack_adamw", tree.handle, bucket, wire.data_ptr(), wire_code(wire.dtype),
+                  int(divisor), theta.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                  *scalars, int(inner_slot), _s(theta))
+
+    def delta_pack_adamw(self, tree, bucket, inner_slot, theta, wire, exp_avg, exp_avg_sq,
+                         scalars) -> None:
+        """One peer, one pass: delta + AdamW + copy-back, the pseudo-gradient kept in `wire`."""
+        _lib.call("dl_delta_pack_adamw", tree.handle, bucket, inner_slot, theta.data_ptr(),
+                  wire.data_ptr(), wire_code(wire.dtype), exp_avg.data_ptr(),
+                  exp_avg_sq.data_ptr(), *scalars, _s(theta))
 
     def pack_sgd_tiled(self, tree, bucket, inner_slot, theta, wire, mom, lr, momentum,
                        nesterov, first, tile_chunks) -> None:

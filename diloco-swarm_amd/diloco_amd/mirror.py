@@ -629,7 +629,12 @@ class DeviceOuterMirror:
     OuterSGD.step() rather than in sync_inner_model (train.py reads neither in between), and
     changing the inner params or θ in place between compute_pseudo_gradient and the call that
     consumes the delta raises instead of being silently used (writes through an inner tensor's
-    `.data` bypass version counters: call invalidate() after them)."""
+    `.data` bypass version counters: call invalidate() after them).
+
+    An AdamW outer optimizer (optim.OuterAdamW) steps through adamw_step the same way: ONE
+    dl_delta_pack_adamw at one peer (36 B/param), dl_unpack_adamw per bucket after the
+    replicated exchange at N > 1; exp_avg and exp_avg_sq are two more packed arenas whose
+    views are the optimizer's state."""
 
     def __init__(self, outer_model: torch.nn.Module, device: torch.device, kernels=None,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = False,
@@ -717,6 +722,14 @@ class DeviceOuterMirror:
         self._mom_shard = None  # (group, n, rank) of the steps that left it sharded
         self.d_recv: Optional[torch.Tensor] = None  # a2a landing arena (the wire's size)
         self._warned = False
+        # an AdamW outer optimizer (optim.OuterAdamW): packed exp_avg / exp_avg_sq arenas, made
+        # at its first fused step; the lists the last step returned (the optimizer's state)
+        self.d_m1: Optional[torch.Tensor] = None
+        self.d_m2: Optional[torch.Tensor] = None
+        self._adam_src = None
+        # set by utils when an OuterAdamW is attached to the outer model and no exchange was
+        # asked for: its fused step needs the whole averaged wire on every rank (replicated)
+        self.adamw_replicated = False
 
     def _momentum_buffer(self, view: torch.Tensor) -> "MomentumBuffer":
         t = view.as_subclass(MomentumBuffer)
@@ -850,7 +863,7 @@ class DeviceOuterMirror:
         return lo + rank * s, lo + (rank + 1) * s
 
     def _exchange_mode(self, n: int, ordered: bool) -> str:
-        mode = "a2a" if ordered else self.exchange
+        mode = "a2a" if ordered else "replicated" if self.adamw_replicated else self.exchange
         if self.wire == "bf16":
             if ordered and not self._warned:
                 self._warned = True
@@ -1337,6 +1350,84 @@ class DeviceOuterMirror:
         self._synced = (target + (tver,)) if write else None
         return bufs
 
+    # ---- the AdamW outer step (optim.OuterAdamW) -------------------------------------------
+    def adamw_ready(self) -> bool:
+        """The fused AdamW pass covers what is pending: a recorded delta (one peer) or the
+        whole wire on this rank (replicated exchange, fp32 or bf16; eager mode). Not the
+        sharded / a2a slices nor the int8 slots: OuterAdamW then runs torch's own step."""
+        return self._delta is not None or self._xmode is None
+
+    def _adam_state(self, host_m, host_v):
+        """The packed exp_avg / exp_avg_sq arenas holding the optimizer's state: zeros when it
+        has none yet; tensors that are not this mirror's views (a loaded state_dict) copied in."""
+        if self.d_m1 is None:
+            self.d_m1 = torch.zeros_like(self.d_theta)
+            self.d_m2 = torch.zeros_like(self.d_theta)
+            for name, arena in (("exp_avg", self.d_m1), ("exp_avg_sq", self.d_m2)):
+                plain = self._make_views(arena)
+                self._views[name + "_plain"] = plain
+                self._views[name] = [self._momentum_buffer(v) for v in plain]
+                self._ptrs[name] = [v.data_ptr() for v in plain]
+            fresh = True
+        else:
+            fresh = False
+        src = self._adam_src
+        ours = (src is not None and len(host_m) == len(src[0]) and len(host_v) == len(src[1])
+                and all(map(is_, host_m, src[0])) and all(map(is_, host_v, src[1])))
+        if not ours:
+            for name, host, arena in (("exp_avg", host_m, self.d_m1),
+                                      ("exp_avg_sq", host_v, self.d_m2)):
+                have = [b is not None for b in host]
+                if any(have) and not all(have):
+                    raise RuntimeError(f"{name} exists for some outer parameters only")
+                with torch.no_grad():
+                    if not any(have):
+                        if not fresh:
+                            arena.zero_()  # the optimizer's state was reset
+                        continue
+                    for b, v, e in zip(host, self._views[name + "_plain"], self._ptrs[name]):
+                        if _DATA_PTR(b) != e or b.device != v.device:
+                            v.copy_(b)  # e.g. a state_dict loaded into the optimizer
+        self._adam_src = (self._views["exp_avg"], self._views["exp_avg_sq"])
+        return self._adam_src
+
+    def adamw_step(self, scalars, host_m, host_v):
+        """torch's _single_tensor_adamw over the whole tree in one pass (scalars:
+        kernels.adamw_scalars); returns the exp_avg and exp_avg_sq tensors (views of the packed
+        arenas) for the optimizer state. One peer: dl_delta_pack_adamw (delta, .grad, AdamW, θ
+        and the inner params); N > 1, replicated: dl_unpack_adamw per bucket, each waiting for
+        its own collective, the pending /n left in the divisor."""
+        if not self.adamw_ready():
+            raise RuntimeError("adamw_step: the pending exchange is not the replicated one")
+        tver = self._theta_version()
+        delta = self._take_delta(tver) if self._delta is not None else None
+        tver = self._relay_theta(tver)
+        if delta is None:
+            self._relay_grads(zero_fill_missing=False)
+        bufs = self._adam_state(host_m, host_v)
+        target, self._target = self._target, None
+        write = target is not None
+        if delta is not None:  # one peer: the delta never leaves registers
+            self.k.delta_pack_adamw(self.tree, ALL, SLOT_INNER, self.d_theta, self.d_wire,
+                                    self.d_m1, self.d_m2, scalars)
+        else:
+            if write:
+                self.k.bind(self.tree, SLOT_INNER, target[0], self.device, key=tuple(target[1]))
+            # a pending /n stays pending: the wire keeps the Σ, .grad settles it when read
+            wire = self.d_wire16 if self._sum16 else self.d_wire
+            slot = SLOT_INNER if write else -1
+            works, self._works = self._works, None
+            if works is None:
+                self.k.unpack_adamw(self.tree, ALL, wire, self._div, self.d_theta, self.d_m1,
+                                    self.d_m2, scalars, slot)
+            else:  # bucket b's pass waits for bucket b's collective only
+                for b, w in enumerate(works):
+                    w.wait()
+                    self.k.unpack_adamw(self.tree, b, wire, self._div, self.d_theta, self.d_m1,
+                                        self.d_m2, scalars, slot)
+        self._synced = (target + (tver,)) if write else None
+        return bufs
+
     def copy_to_inner(self, inner_params: Sequence[torch.Tensor]) -> None:
         """inner = outer (src/utils.py:223-226): verified no-op after a fused step that
         already wrote these inner params, else scattered from HBM."""
@@ -1517,7 +1608,8 @@ class HostParameter(torch.nn.Parameter):
         return out
 
 
-_ARENAS = ("grad", "theta", "mom")
+_ARENAS = ("grad", "theta", "mom", "exp_avg", "exp_avg_sq")
+_ADAM_ARENAS = ("exp_avg", "exp_avg_sq")
 
 
 class LazyHostOuterMirror:
@@ -1536,7 +1628,9 @@ class LazyHostOuterMirror:
     `.data` / `.grad`). So every value a caller observes is the reference's, on the CPU,
     while an outer step that nobody observes costs what the device placement costs. Under an
     opted-in sharded exchange at N > 1, reading `.grad` or the momentum is a collective over
-    the DP group, as for the device placement (collective_read guards it)."""
+    the DP group, as for the device placement (collective_read guards it). With an AdamW outer
+    optimizer (optim.OuterAdamW, adamw_step) exp_avg and exp_avg_sq are two more host arenas,
+    kept coherent the same way."""
 
     def __init__(self, outer_model: torch.nn.Module, device: torch.device, kernels=None,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = True,
@@ -1564,7 +1658,8 @@ class LazyHostOuterMirror:
         from .utils import env_flag
 
         self._pin = self.device.type == "cuda" and env_flag("DILOCO_HOST_PIN", False)
-        self.h = {"theta": self._arena(zero=True), "grad": self._arena(), "mom": None}
+        self.h = {"theta": self._arena(zero=True), "grad": self._arena(), "mom": None,
+                  "exp_avg": None, "exp_avg_sq": None}
         ref = weakref.ref(self)
         with _NO_TF(), torch.no_grad():
             self._theta_views = self._views(self.h["theta"])
@@ -1577,8 +1672,9 @@ class LazyHostOuterMirror:
             self._grad_views = [self._host_tensor(v, "grad") for v in self._views(self.h["grad"])]
         self.params = params
         self._mom_views: Optional[List[torch.Tensor]] = None
+        self._adam_views = None  # (exp_avg, exp_avg_sq) HostTensor views, after an AdamW step
         self._ver = {"theta": self.h["theta"]._version, "grad": self.h["grad"]._version,
-                     "mom": None}
+                     "mom": None, "exp_avg": None, "exp_avg_sq": None}
         self._dirty: set = set()
         self._written: set = set()  # arenas written on the host since the last upload
         self._grads_set = False  # the API .grads are the grad arena's views
@@ -1626,7 +1722,8 @@ class LazyHostOuterMirror:
                 self.dev.settle_grads()  # the pending delta / Σ / sharded gathers, then /n
             elif arena == "mom":
                 self.dev.gather_momentum()
-            src = {"theta": self.dev.d_theta, "grad": self.dev.d_wire, "mom": self.dev.d_mom}[arena]
+            src = {"theta": self.dev.d_theta, "grad": self.dev.d_wire, "mom": self.dev.d_mom,
+                   "exp_avg": self.dev.d_m1, "exp_avg_sq": self.dev.d_m2}[arena]
             h = self.h[arena]
             h.copy_(src, non_blocking=self._pin)
             self._sync_stream()
@@ -1642,7 +1739,7 @@ class LazyHostOuterMirror:
         re-upload every host arena at the next call."""
         self.dev.invalidate()
         self.theta_touched = self.grads_touched = True
-        self._written |= {"theta", "grad", "mom"}
+        self._written |= set(_ARENAS)
 
     def host_written(self, arena: str) -> None:
         self._written.add(arena)
@@ -1740,6 +1837,39 @@ class LazyHostOuterMirror:
             self._ver["mom"] = self.h["mom"]._version
         self._dirty.add("mom")
         return self._mom_views
+
+    def adamw_ready(self) -> bool:
+        return self.dev.adamw_ready()
+
+    def adamw_step(self, scalars, host_m, host_v):
+        """DeviceOuterMirror.adamw_step on the HBM twin; the optimizer's exp_avg / exp_avg_sq
+        are HostTensor views of two more host arenas, refreshed from HBM when read."""
+        self._push()
+        dev = self.dev
+        dev_m, dev_v = host_m, host_v
+        mine = self._adam_views
+        if (mine is not None and len(host_m) == len(mine[0]) and len(host_v) == len(mine[1])
+                and all(map(is_, host_m, mine[0])) and all(map(is_, host_v, mine[1]))):
+            for a, d in zip(_ADAM_ARENAS, (dev.d_m1, dev.d_m2)):
+                if self._changed(a, a):  # written on the host: upload
+                    with _NO_TF():
+                        d.copy_(self.h[a], non_blocking=self._pin)
+                    self._ver[a] = self.h[a]._version
+            dev_m, dev_v = dev._views["exp_avg"], dev._views["exp_avg_sq"]  # the device's own
+        else:
+            for a in _ADAM_ARENAS:  # foreign state replaces the arenas' content on both sides
+                self._written.discard(a)
+        dev.adamw_step(scalars, dev_m, dev_v)
+        self._dirty.add("theta")
+        if mine is None:
+            views = []
+            for a in _ADAM_ARENAS:
+                self.h[a] = self._arena()
+                views.append([self._host_tensor(v, a) for v in self._views(self.h[a])])
+                self._ver[a] = self.h[a]._version
+            self._adam_views = mine = tuple(views)
+        self._dirty.update(_ADAM_ARENAS)
+        return mine
 
     def copy_to_inner(self, inner_params: Sequence[torch.Tensor]) -> None:
         self._push()

@@ -8,6 +8,9 @@ dl_unpack_sgd launch on the device mirror of the outer model (mirror.HostOuterMi
 writes θ and the momentum buffers back to the host tensors the optimizer owns; on the device
 outer model (mirror.DeviceOuterMirror) its state's momentum buffers are views of the packed
 HBM momentum (mirror.MomentumBuffer).
+
+With cfg.type == "AdamW" (src/utils.py:60-61) and DILOCO_OUTER_ADAMW=fused it returns an
+`OuterAdamW`: torch.optim.AdamW's interface over dl_delta_pack_adamw / dl_unpack_adamw.
 """
 from __future__ import annotations
 
@@ -15,11 +18,13 @@ import inspect
 from operator import is_, methodcaller
 
 import torch
-from torch.optim import SGD
+from torch.optim import SGD, AdamW
 
+from .kernels import adamw_scalars
 from .mirror import HostOuterMirror
 
 _MOMENTUM_BUFFER = methodcaller("get", "momentum_buffer")
+_ADAM_KEYS = ("step", "exp_avg", "exp_avg_sq")
 
 
 class OuterSGD(SGD):
@@ -94,4 +99,102 @@ class OuterSGD(SGD):
             else:
                 for p, b in zip(params, bufs):
                     st[p]["momentum_buffer"] = b
+        return loss
+
+
+class OuterAdamW(AdamW):
+    """The AdamW outer optimizer (src/utils.py:60-61, configs/optimizer/adamw.toml) with its
+    step fused into the outer model's mirror: at one peer the whole outer step is one
+    dl_delta_pack_adamw pass (36 B/param), at N > 1 one dl_unpack_adamw pass per bucket after
+    the replicated exchange. It IS a torch.optim.AdamW (param_groups, hooks, LR schedulers and
+    state_dict work unchanged; state[p]["step"] is torch's fp32 scalar tensor, exp_avg and
+    exp_avg_sq are views of the mirror's packed arenas), selected by get_optimizer under
+    DILOCO_OUTER_ADAMW=fused.
+
+    The fused pass is one element of torch's _single_tensor_adamw (include/diloco_hip.h).
+    Whenever that contract or the mirror does not cover the step -- amsgrad, maximize,
+    capturable, differentiable, beta1 <= 0.5, tensor hyper-parameters, more than one group,
+    parameters whose step counts differ, a sharded / a2a / int8 exchange, write_back "sync" or
+    "deferred", no mirror at all (a CPU-only run) -- step() runs torch's own step body, exactly
+    what a stock AdamW on this outer model does: never a silently different result."""
+
+    def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas=(0.9, 0.999),
+                 weight_decay: float = 1e-2, eps: float = 1e-8, **kw):
+        super().__init__(model.parameters(), lr=lr, betas=betas, eps=eps,
+                         weight_decay=weight_decay, **kw)
+        self._model = model
+        from .utils import mark_adamw_outer
+
+        mark_adamw_outer(model)  # an unrequested exchange becomes the replicated one
+
+    def state_dict(self):
+        """torch.optim.AdamW.state_dict, after the mirror's pending work landed."""
+        from .utils import flush_outer_model
+
+        flush_outer_model(self._model)
+        return super().state_dict()
+
+    def _fused_plan(self):
+        """(mirror, scalars of this step, exp_avg list, exp_avg_sq list, states) when the
+        fused pass computes exactly what torch's step body would; else None."""
+        if len(self.param_groups) != 1:
+            return None
+        g = self.param_groups[0]
+        if (g["amsgrad"] or g["maximize"] or g.get("capturable") or g.get("differentiable")
+                or g.get("fused") or not g.get("decoupled_weight_decay", True)):
+            return None
+        hyper = (g["lr"], g["betas"][0], g["betas"][1], g["weight_decay"], g["eps"])
+        if any(isinstance(x, torch.Tensor) for x in hyper):
+            return None
+        lr, beta1, beta2, wd, eps = map(float, hyper)
+        if not beta1 > 0.5:  # torch's lerp switches formula at weight 0.5
+            return None
+        mirror = getattr(self._model, "_diloco_mirror", None)  # utils._ATTR
+        if mirror is None or not hasattr(mirror, "adamw_step") or not mirror.adamw_ready():
+            return None
+        params = g["params"]
+        if len(params) != len(mirror.params) or not all(map(is_, params, mirror.params)):
+            return None
+        states = [self.state[p] for p in params]
+        have = [len(s) != 0 for s in states]
+        if any(have) and not all(have):
+            return None
+        step = 0.0
+        if have[0]:
+            if any(set(s) != set(_ADAM_KEYS) for s in states):
+                return None
+            steps = [s["step"] for s in states]
+            if any(t.device.type != "cpu" for t in steps):
+                return None
+            step = float(steps[0])
+            if any(float(t) != step for t in steps):
+                return None
+        scalars = adamw_scalars(lr, beta1, beta2, wd, eps, step + 1.0)
+        return (mirror, scalars, [s.get("exp_avg") for s in states],
+                [s.get("exp_avg_sq") for s in states], states)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        """One outer AdamW step (src/train.py:267), wrapped by torch.optim.Optimizer like every
+        optimizer's step (profiler annotation, pre / post hooks)."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        plan = self._fused_plan()
+        if plan is None:
+            # torch's own step body, unwrapped: this call already runs inside the hook wrapper
+            inspect.unwrap(AdamW.step)(self)
+            return loss
+        mirror, scalars, host_m, host_v, states = plan
+        ms, vs = mirror.adamw_step(scalars, host_m, host_v)
+        if not states[0]:
+            from torch.optim.optimizer import _get_scalar_dtype
+
+            for s in states:
+                s["step"] = torch.tensor(0.0, dtype=_get_scalar_dtype())
+        torch._foreach_add_([s["step"] for s in states], 1)
+        if not all(map(is_, host_m, ms)) or not all(map(is_, host_v, vs)):
+            for s, m, v in zip(states, ms, vs):
+                s["exp_avg"], s["exp_avg_sq"] = m, v
         return loss

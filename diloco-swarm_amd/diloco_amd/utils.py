@@ -12,6 +12,12 @@ it raises. On the GPU:
   sync_inner_model(out, in)         in = out              (dl_scatter)      src/utils.py:223-226
   get_optimizer(model, cfg)         AdamW | SGD (outer: OuterSGD, HIP)      src/utils.py:59-65
 
+An AdamW outer optimizer (configs/optimizer/adamw.toml) is stock torch.optim.AdamW unless
+DILOCO_OUTER_ADAMW=fused: then get_optimizer returns optim.OuterAdamW for an outer model, whose
+step is one dl_delta_pack_adamw pass at one peer (36 B/param) and one dl_unpack_adamw pass per
+bucket at N > 1; an outer model it is attached to takes the replicated exchange when none was
+asked for, and anything its kernels do not cover (see optim.OuterAdamW) runs torch's own step.
+
 Placement of the outer model (`get_outer_model(..., placement=)`, default from the
 DILOCO_OUTER_PLACEMENT environment variable, "host" if unset):
 
@@ -59,7 +65,7 @@ from torch.optim import SGD, AdamW, Optimizer
 from .kernels import default_kernels
 from .mirror import (DEFAULT_EXCHANGE, OUTER_EXCHANGES, OUTER_WIRES, WRITE_BACKS,
                      DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
-from .optim import OuterSGD
+from .optim import OuterAdamW, OuterSGD
 from .plan import DEFAULT_BUCKET_CAP_ELEMS
 
 _ATTR = "_diloco_mirror"
@@ -69,6 +75,9 @@ _WRITE_BACK = "_diloco_write_back"
 _FUSED = "_diloco_fused"
 _WIRE = "_diloco_wire"
 _EXCHANGE = "_diloco_exchange"
+_EXCHANGE_ASKED = "_diloco_exchange_asked"  # by argument or DILOCO_OUTER_EXCHANGE
+_ADAMW = "_diloco_adamw"  # an optim.OuterAdamW is attached
+OUTER_ADAMW = ("torch", "fused")
 _PENDING = "_diloco_pending_device"  # placement="device" built before the inner model moved
 PLACEMENTS = ("host", "device")
 _TRUE = ("1", "true", "on", "yes")
@@ -100,6 +109,25 @@ def has_mirror(outer_model: nn.Module) -> bool:
     return getattr(outer_model, _ATTR, None) is not None
 
 
+def _apply_adamw_mark(outer_model: nn.Module, m) -> None:
+    """An outer model with an OuterAdamW attached and no exchange asked for takes the
+    replicated exchange (the device placement's implicit sharded default does not apply): the
+    fused AdamW pass needs the whole averaged wire, and .grad and the state stay local."""
+    dev = getattr(m, "dev", m)  # the lazy host mirror's HBM twin
+    if hasattr(dev, "adamw_replicated"):
+        dev.adamw_replicated = bool(getattr(outer_model, _ADAMW, False)
+                                    and not getattr(outer_model, _EXCHANGE_ASKED, False))
+
+
+def mark_adamw_outer(outer_model: nn.Module) -> None:
+    """Called by optim.OuterAdamW at construction: the model's mirror (now or when it is
+    created) sees the mark in all_reduce."""
+    object.__setattr__(outer_model, _ADAMW, True)
+    m = getattr(outer_model, _ATTR, None)
+    if m is not None:
+        _apply_adamw_mark(outer_model, m)
+
+
 def outer_mirror(outer_model: nn.Module, device=None):
     """The device mirror of an outer model (created on first use): HostOuterMirror for the
     reference's host placement, DeviceOuterMirror for placement="device"."""
@@ -128,6 +156,7 @@ def outer_mirror(outer_model: nn.Module, device=None):
                                                    DEFAULT_EXCHANGE["device"]),
                                   keep_params=keep)
             object.__setattr__(outer_model, _ATTR, m)
+            _apply_adamw_mark(outer_model, m)
             return m
         if device is None:
             device = getattr(k, "default_device", None)
@@ -147,6 +176,7 @@ def outer_mirror(outer_model: nn.Module, device=None):
         else:
             m = HostOuterMirror(outer_model, torch.device(device), kernels=k, write_back=wb)
         object.__setattr__(outer_model, _ATTR, m)  # not a submodule / not in state_dict
+        _apply_adamw_mark(outer_model, m)
     return m
 
 
@@ -185,7 +215,10 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     if wire not in OUTER_WIRES:
         raise ValueError(f"wire {wire!r}: one of {OUTER_WIRES}")
     if exchange is None:
-        exchange = os.environ.get("DILOCO_OUTER_EXCHANGE") or DEFAULT_EXCHANGE[placement]
+        exchange = os.environ.get("DILOCO_OUTER_EXCHANGE") or None
+    asked = exchange is not None
+    if not asked:
+        exchange = DEFAULT_EXCHANGE[placement]
     if exchange not in OUTER_EXCHANGES:
         raise ValueError(f"exchange {exchange!r}: one of {OUTER_EXCHANGES}")
     lazy = placement == "device" or write_back == "lazy"  # the outer step runs on an HBM copy
@@ -215,6 +248,7 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     object.__setattr__(outer_model, _FUSED, bool(fused) and lazy)
     object.__setattr__(outer_model, _WIRE, wire)
     object.__setattr__(outer_model, _EXCHANGE, exchange)
+    object.__setattr__(outer_model, _EXCHANGE_ASKED, asked)
     if placement == "device" and has_params and not getattr(outer_model, _PENDING, False):
         # lay the parameters out in the packed HBM arena now (fused: as OuterParameters);
         # a model without parameters keeps none: the four calls are the reference's empty loops
@@ -279,8 +313,16 @@ def sync_inner_model(outer_model: nn.Module, inner_model: nn.Module) -> None:
 
 
 def get_optimizer(model: nn.Module, optimizer_config) -> Optimizer:
-    """src/utils.py:59-65. SGD on the outer model (from get_outer_model) -> OuterSGD."""
+    """src/utils.py:59-65. SGD on the outer model (from get_outer_model) -> OuterSGD; AdamW on
+    it under DILOCO_OUTER_ADAMW=fused -> OuterAdamW (unset or "torch": stock AdamW)."""
     if optimizer_config.type == "AdamW":
+        knob = (os.environ.get("DILOCO_OUTER_ADAMW") or "torch").strip().lower()
+        if knob not in OUTER_ADAMW:
+            raise ValueError(f"DILOCO_OUTER_ADAMW={knob!r}: one of {OUTER_ADAMW}")
+        if knob == "fused" and getattr(model, _OUTER, False):
+            return OuterAdamW(model, lr=optimizer_config.lr,
+                              weight_decay=optimizer_config.weight_decay,
+                              betas=optimizer_config.betas)
         return AdamW(model.parameters(), lr=optimizer_config.lr,
                      weight_decay=optimizer_config.weight_decay, betas=optimizer_config.betas)
     elif optimizer_config.type == "SGD":

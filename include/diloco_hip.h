@@ -30,7 +30,7 @@ extern "C" {
 
 #define DL_API __attribute__((visibility("default")))
 
-#define DL_ABI_VERSION 2
+#define DL_ABI_VERSION 3
 #define DL_ALIGN_ELEMS 64      /* segment start alignment in the packed space: 256 B of fp32 */
 #define DL_CHUNK_ELEMS 4096    /* work unit of every segment walker: 16 KiB of fp32 */
 #define DL_ALL_BUCKETS (-1)
@@ -168,6 +168,36 @@ DL_API int dl_delta_pack_sgd(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
                              float* outer_packed, void* wire, int32_t wire_dtype,
                              float* mom_packed, float lr, float momentum, int32_t nesterov,
                              int32_t first_step, dl_stream_t stream);
+
+/* a3+a4+a5 fused for an AdamW outer optimizer (src/utils.py:60-61, configs/optimizer/adamw.toml,
+ * stepped at src/train.py:267): one element of torch's _single_tensor_adamw (amsgrad, maximize
+ * and capturable off; beta1 > 0.5, where torch's lerp uses this formula), then sync_inner_model.
+ * The caller computes the scalars in doubles exactly as torch does and narrows each to fp32
+ * once: decay = 1 - lr*wd, w1 = 1 - beta1, w2 = 1 - beta2, neg_step_size = -(lr / (1 - beta1^t)),
+ * bc2_sqrt = (1 - beta2^t)^0.5, t the step count after this step.
+ *   g = wire/divisor                      (IEEE division; divisor 1: untouched)
+ *   θ = θ*decay;  m = fma(w1, g - m, m);  v = v*beta2;  v = fma(w2*g, g, v)
+ *   den = sqrt(v)/bc2_sqrt + eps          (correctly rounded sqrt and division)
+ *   θ = θ + (neg_step_size*m)/den;  inner[seg][j] = θ
+ * Every other operation rounds on its own. exp_avg (m) and exp_avg_sq (v) are packed fp32
+ * buffers; zeros are the first step. inner_slot < 0 skips the inner write. 32 B/param (fp32
+ * wire; 28 without the inner write). */
+DL_API int dl_unpack_adamw(dl_tree_t tree, int32_t bucket, const void* wire, int32_t wire_dtype,
+                           int32_t divisor, float* outer_packed, float* exp_avg_packed,
+                           float* exp_avg_sq_packed, float decay, float w1, float beta2, float w2,
+                           float neg_step_size, float bc2_sqrt, float eps, int32_t inner_slot,
+                           dl_stream_t stream);
+
+/* a2+a3+a4+a5 at ONE peer for an AdamW outer optimizer, keeping the pseudo-gradient:
+ *   g = θ - inner[seg][j]; wire[k] = g (bf16 wire: RNE, and AdamW uses the rounded value);
+ *   AdamW as dl_unpack_adamw (divisor 1); θ and inner[seg][j] <- new θ
+ * One pass: 36 B/param (fp32 wire: 16 read, 20 written) instead of 12 + 32 for dl_delta_pack +
+ * dl_unpack_adamw, bit-identical to that pair (wire included). */
+DL_API int dl_delta_pack_adamw(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
+                               float* outer_packed, void* wire, int32_t wire_dtype,
+                               float* exp_avg_packed, float* exp_avg_sq_packed, float decay,
+                               float w1, float beta2, float w2, float neg_step_size,
+                               float bc2_sqrt, float eps, dl_stream_t stream);
 
 /* a2 -> a3 -> a4 -> a5 at ONE peer as the two-kernel pipeline (dl_delta_pack then
  * dl_unpack_sgd with divisor 1; src/utils.py:221, src/comm.py:118-119, src/train.py:267,
