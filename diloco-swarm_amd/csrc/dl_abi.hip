@@ -423,13 +423,6 @@ int make_launch(dl_tree_t t, int32_t b, dl_stream_t s, dl::Launch* L, const char
   L->grid = t->grid;
   L->flags = t->flags == DL_TUNE_AUTO ? auto_flags : t->flags;
   L->pairs = (L->flags & DL_TUNE_PAIRS) != 0;
-#ifdef DL_XCD_XLOG  // A/B builds (tools/store_order_ab.py): one mapping for every launch
-  L->xlog = DL_XCD_XLOG;
-#else
-  // the dispatcher's interleave: runs of B chunks per XCD change the headline kernel's time by
-  // -3.4 ... +2.0 % depending on the box (profiles/r06_store_order_ab_*)
-  L->xlog = 0;
-#endif
   if (t->flags == DL_TUNE_AUTO && big != Big::keep && L->c1 - L->c0 >= kBigLaunchChunks) {
     L->flags |= DL_TUNE_NT_STORES;
     if ((big == Big::nt_stores_2 || big == Big::two_chunks) && L->grid == 0)
@@ -462,6 +455,16 @@ int check_dtype(int32_t d, const char* who) {
     int rc_ = (x);        \
     if (rc_) return rc_;  \
   } while (0)
+
+// The SGD entry points' hyper-parameters: a momentum needs its buffer, Nesterov needs a momentum
+int sgd_args(const char* who, const float* mom, float lr, float momentum, int32_t nesterov,
+             int32_t first_step, dl::SgdArgs* a) {
+  if (momentum != 0.f) DL_TRY(check_packed(mom, who, "momentum"));
+  if (nesterov && momentum == 0.f)
+    return fail(DL_E_ARG, "%s: Nesterov momentum requires a momentum", who);
+  *a = dl::SgdArgs{-lr, momentum, nesterov ? 1 : 0, first_step ? 1 : 0};
+  return DL_OK;
+}
 
 }  // namespace
 
@@ -506,12 +509,10 @@ DL_API int dl_unpack_sgd(dl_tree_t t, int32_t b, const void* wire, int32_t wire_
   DL_TRY(check_packed(wire, "dl_unpack_sgd", "wire"));
   DL_TRY(check_dtype(wire_dtype, "dl_unpack_sgd"));
   DL_TRY(check_packed(outer, "dl_unpack_sgd", "outer"));
-  if (momentum != 0.f) DL_TRY(check_packed(mom, "dl_unpack_sgd", "momentum"));
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_unpack_sgd", mom, lr, momentum, nesterov, first_step, &a));
   DL_TRY(check_slot(t, inner_slot, "dl_unpack_sgd", true));
   if (divisor < 1) return fail(DL_E_ARG, "dl_unpack_sgd: divisor %d", divisor);
-  if (nesterov && momentum == 0.f)
-    return fail(DL_E_ARG, "dl_unpack_sgd: Nesterov momentum requires a momentum");
-  dl::SgdArgs a{-lr, momentum, nesterov ? 1 : 0, first_step ? 1 : 0};
   DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_sgd"));
   hipError_t e = dl::launch_unpack_sgd(L, wire, wire_dtype, divisor, outer, mom, a, inner_slot);
   return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_sgd") : hip_fail(e, "dl_unpack_sgd");
@@ -524,10 +525,8 @@ DL_API int dl_delta_sgd(dl_tree_t t, int32_t b, int32_t inner_slot, float* outer
   DL_TRY(make_launch(t, b, s, &L, "dl_delta_sgd", kAutoUnpackSgd));
   DL_TRY(check_slot(t, inner_slot, "dl_delta_sgd"));
   DL_TRY(check_packed(outer, "dl_delta_sgd", "outer"));
-  if (momentum != 0.f) DL_TRY(check_packed(mom, "dl_delta_sgd", "momentum"));
-  if (nesterov && momentum == 0.f)
-    return fail(DL_E_ARG, "dl_delta_sgd: Nesterov momentum requires a momentum");
-  dl::SgdArgs a{-lr, momentum, nesterov ? 1 : 0, first_step ? 1 : 0};
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_delta_sgd", mom, lr, momentum, nesterov, first_step, &a));
   DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_delta_sgd"));
   hipError_t e = dl::launch_delta_sgd(L, inner_slot, outer, mom, a);
   return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_sgd") : hip_fail(e, "dl_delta_sgd");
@@ -542,10 +541,8 @@ DL_API int dl_delta_pack_sgd(dl_tree_t t, int32_t b, int32_t inner_slot, float* 
   DL_TRY(check_packed(outer, "dl_delta_pack_sgd", "outer"));
   DL_TRY(check_packed(wire, "dl_delta_pack_sgd", "wire"));
   DL_TRY(check_dtype(wire_dtype, "dl_delta_pack_sgd"));
-  if (momentum != 0.f) DL_TRY(check_packed(mom, "dl_delta_pack_sgd", "momentum"));
-  if (nesterov && momentum == 0.f)
-    return fail(DL_E_ARG, "dl_delta_pack_sgd: Nesterov momentum requires a momentum");
-  dl::SgdArgs a{-lr, momentum, nesterov ? 1 : 0, first_step ? 1 : 0};
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_delta_pack_sgd", mom, lr, momentum, nesterov, first_step, &a));
   DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_delta_pack_sgd"));
   hipError_t e = dl::launch_delta_pack_sgd(L, inner_slot, outer, wire, wire_dtype, mom, a);
   return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_pack_sgd") : hip_fail(e, "dl_delta_pack_sgd");
@@ -608,11 +605,9 @@ DL_API int dl_pack_sgd_tiled(dl_tree_t t, int32_t b, int32_t inner_slot, float* 
   DL_TRY(check_packed(outer, "dl_pack_sgd_tiled", "outer"));
   DL_TRY(check_packed(wire, "dl_pack_sgd_tiled", "wire"));
   DL_TRY(check_dtype(wire_dtype, "dl_pack_sgd_tiled"));
-  if (momentum != 0.f) DL_TRY(check_packed(mom, "dl_pack_sgd_tiled", "momentum"));
-  if (nesterov && momentum == 0.f)
-    return fail(DL_E_ARG, "dl_pack_sgd_tiled: Nesterov momentum requires a momentum");
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_pack_sgd_tiled", mom, lr, momentum, nesterov, first_step, &a));
   if (tile_chunks < 0) return fail(DL_E_ARG, "dl_pack_sgd_tiled: tile_chunks %d", tile_chunks);
-  const dl::SgdArgs a{-lr, momentum, nesterov ? 1 : 0, first_step ? 1 : 0};
   DL_TRY(slot_begin(t, inner_slot, P.stream, "dl_pack_sgd_tiled"));
   const int32_t c0 = P.c0, c1 = P.c1;
   const int32_t step = tile_chunks > 0 ? tile_chunks : (c1 - c0 > 0 ? c1 - c0 : 1);
@@ -636,13 +631,11 @@ DL_API int dl_shard_sgd(const void* wire, int32_t wire_dtype, int32_t divisor, f
   DL_TRY(check_packed(wire, "dl_shard_sgd", "wire"));
   DL_TRY(check_dtype(wire_dtype, "dl_shard_sgd"));
   DL_TRY(check_packed(outer, "dl_shard_sgd", "outer"));
-  if (momentum != 0.f) DL_TRY(check_packed(mom, "dl_shard_sgd", "momentum"));
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_shard_sgd", mom, lr, momentum, nesterov, first_step, &a));
   if (divisor < 1) return fail(DL_E_ARG, "dl_shard_sgd: divisor %d", divisor);
-  if (nesterov && momentum == 0.f)
-    return fail(DL_E_ARG, "dl_shard_sgd: Nesterov momentum requires a momentum");
   if ((n + DL_CHUNK_ELEMS - 1) / DL_CHUNK_ELEMS > INT32_MAX)
     return fail(DL_E_ARG, "dl_shard_sgd: shard too large");
-  dl::SgdArgs a{-lr, momentum, nesterov ? 1 : 0, first_step ? 1 : 0};
   hipError_t e = dl::launch_shard_sgd(wire, wire_dtype, divisor, outer, mom, n, a,
                                       static_cast<hipStream_t>(s));
   return e == hipSuccess ? DL_OK : hip_fail(e, "dl_shard_sgd");
@@ -658,10 +651,8 @@ DL_API int dl_shard_reduce_sgd(const void* slices, int32_t wire_dtype, int32_t n
   DL_TRY(check_packed(slices, "dl_shard_reduce_sgd", "slices"));
   DL_TRY(check_dtype(wire_dtype, "dl_shard_reduce_sgd"));
   DL_TRY(check_packed(outer, "dl_shard_reduce_sgd", "outer"));
-  if (momentum != 0.f) DL_TRY(check_packed(mom, "dl_shard_reduce_sgd", "momentum"));
-  if (nesterov && momentum == 0.f)
-    return fail(DL_E_ARG, "dl_shard_reduce_sgd: Nesterov momentum requires a momentum");
-  dl::SgdArgs a{-lr, momentum, nesterov ? 1 : 0, first_step ? 1 : 0};
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_shard_reduce_sgd", mom, lr, momentum, nesterov, first_step, &a));
   hipError_t e = dl::launch_slices_sgd(slices, wire_dtype, n_slices, len, outer, mom, a,
                                        static_cast<hipStream_t>(s));
   return e == hipSuccess ? DL_OK : hip_fail(e, "dl_shard_reduce_sgd");
@@ -809,9 +800,8 @@ int xgmi_step(const char* who, bool delta, const uint64_t* srcs, const uint64_t*
   if (lo < 0 || len < 0 || lo % 4 || len % 4)
     return fail(DL_E_ARG, "%s: shard [%lld, +%lld) not a multiple of 4", who, (long long)lo,
                 (long long)len);
-  if (momentum != 0.f) DL_TRY(check_packed(mom, who, "momentum"));
-  if (nesterov && momentum == 0.f)
-    return fail(DL_E_ARG, "%s: Nesterov momentum requires a momentum", who);
+  dl::SgdArgs a;
+  DL_TRY(sgd_args(who, mom, lr, momentum, nesterov, first_step, &a));
   dl::XgmiPeers p{};
   for (int32_t q = 0; q < n; ++q) {
     p.wire[q] = reinterpret_cast<const float*>(srcs[q]);
@@ -819,7 +809,6 @@ int xgmi_step(const char* who, bool delta, const uint64_t* srcs, const uint64_t*
     DL_TRY(check_packed(p.wire[q], who, delta ? "inner" : "wire"));
     DL_TRY(check_packed(p.theta[q], who, "theta"));
   }
-  dl::SgdArgs a{-lr, momentum, nesterov ? 1 : 0, first_step ? 1 : 0};
   hipError_t e = dl::launch_xgmi_reduce_sgd(p, n, rank, lo, len, mom, a, delta,
                                             static_cast<hipStream_t>(s));
   return e == hipSuccess ? DL_OK : hip_fail(e, who);
@@ -874,11 +863,9 @@ DL_API int dl_unpack_sgd_q8(dl_tree_t t, int32_t b, const void* slots, float* ou
   DL_TRY(make_launch(t, b, s, &L, "dl_unpack_sgd_q8", kAutoNT));
   DL_TRY(check_packed(slots, "dl_unpack_sgd_q8", "slots"));
   DL_TRY(check_packed(outer, "dl_unpack_sgd_q8", "outer"));
-  if (momentum != 0.f) DL_TRY(check_packed(mom, "dl_unpack_sgd_q8", "momentum"));
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_unpack_sgd_q8", mom, lr, momentum, nesterov, first_step, &a));
   DL_TRY(check_slot(t, inner_slot, "dl_unpack_sgd_q8", true));
-  if (nesterov && momentum == 0.f)
-    return fail(DL_E_ARG, "dl_unpack_sgd_q8: Nesterov momentum requires a momentum");
-  dl::SgdArgs a{-lr, momentum, nesterov ? 1 : 0, first_step ? 1 : 0};
   DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_sgd_q8"));
   hipError_t e = dl::launch_unpack_sgd_q8(L, static_cast<const uint8_t*>(slots), outer, mom, a,
                                           inner_slot);

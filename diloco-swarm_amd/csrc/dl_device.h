@@ -1,5 +1,7 @@
 // Device-side building blocks shared by the kernel translation units (dl_kernels.hip,
-// dl_q8.hip, dl_adamw.hip): streaming memory ops, element conversions, the segment walker and its launcher.
+// dl_q8.hip, dl_adamw.hip, dl_xgmi.hip): streaming memory ops, element conversions, the segment
+// walker and its launcher, and the element arithmetic of the two update rules (sgd1, adam1).
+// The outer-step body built from them is dl_outer_step.h.
 #pragma once
 #include <type_traits>
 
@@ -60,18 +62,6 @@ constexpr int kAuxSc1 = 16;  // buffer-op cache policy bits, gfx950: sc0 = 1, nt
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t stream_rsrc(void* p) {
   return __builtin_amdgcn_make_buffer_rsrc(p, 0, 0x7fffffff, 0x00020000);
 }
-// Store-order A/B of dl_delta_pack_sgd (tools/store_order_ab.py builds the variants; the
-// product build uses the defaults): DL_DPS_ORDER picks the order of its four output streams,
-// DL_DPS_WIRE_PLAIN stores the wire with plain stores while θ, momentum and inner follow the
-// launch's store policy.
-#ifndef DL_DPS_ORDER
-#define DL_DPS_ORDER 0
-#endif
-#ifdef DL_DPS_WIRE_PLAIN
-#define DL_DPS_WIRE_NTS(n) kStPlain
-#else
-#define DL_DPS_WIRE_NTS(n) (n)
-#endif
 template <int SP>
 __device__ __forceinline__ void stf4(float* p, int v, float4 x) {
   const f32x4 r = {x.x, x.y, x.z, x.w};
@@ -165,37 +155,26 @@ __device__ __forceinline__ T* slot_ptr(void* const* caddr, int nchunk, int slot,
 // DL_TUNE_AUTO selects: non-temporal loads with plain or non-temporal stores. `make TUNING=1`
 // (-DDL_TUNING) instantiates the whole matrix -- plain loads, write-through for every body --
 // for the measurement tools (tools/cold_sweep.py); dl_tree_tune rejects the rest otherwise.
-// Workgroup -> chunk. The dispatcher hands workgroup b to XCD (b + k) mod 8 (k fixed within a
-// dispatch: tools/fill_census.hip), so by default the eight XCDs walk the range interleaved
-// chunk by chunk. With one workgroup per chunk, xlog > 0 makes XCD x walk runs of B = 2^xlog
-// consecutive chunks -- its k-th workgroup takes chunk ((k >> xlog) * 8 + x) * B + (k & (B-1))
-// -- over the whole super-blocks of 8B chunks, the tail as by default; xlog = -1 gives XCD x
-// the x-th eighth of the range in order (n = 8q + r: XCDs below r take q + 1 chunks). Both
-// are bijections on [0, n). The product launches with xlog = 0; the others are A/B builds
-// (tools/store_order_ab.py: no mapping gains on every box).
-__device__ __forceinline__ int32_t walk_index(int32_t b, int32_t n, int32_t xlog) {
-  if (xlog == 0 || int32_t(gridDim.x) != n) return b;
-  const int32_t x = b & 7, k = b >> 3;
-  if (xlog < 0) {
-    const int32_t q = n >> 3, r = n & 7;
-    return x * q + (x < r ? x : r) + k;
-  }
-  const int32_t full = (n >> (xlog + 3)) << (xlog + 3);
-  if (b >= full) return b;
-  return (((k >> xlog) << 3) + x) * (1 << xlog) + (k & ((1 << xlog) - 1));
-}
-
 template <class Body, bool NTL, int NTS>
 __global__ void __launch_bounds__(kThreads)
     k_walk(const Chunk* __restrict__ chunks, int32_t c0, int32_t c1, void* const* __restrict__ caddr,
-           int32_t nchunk, int32_t xlog, Body body) {
-  for (int32_t i0 = int32_t(blockIdx.x); i0 < c1 - c0; i0 += int32_t(gridDim.x)) {
-    const int32_t c = c0 + walk_index(i0, c1 - c0, xlog);
+           int32_t nchunk, Body body) {
+  for (int32_t c = c0 + int32_t(blockIdx.x); c < c1; c += int32_t(gridDim.x)) {
     const Chunk ck = chunks[c];
     body.template run<NTL, NTS>(ck, c, caddr, nchunk, int(threadIdx.x));
   }
 }
 
+// ---- the element arithmetic of the update rules ---------------------------------------------
+// Numerics follow the reference exactly (compiled with -ffp-contract=off and correctly
+// rounded fp32 division):
+//   delta      : outer - inner                         (src/utils.py:221)
+//   average    : sum / n, IEEE true division            (src/comm.py:123)
+//   SGD        : torch _single_tensor_sgd as used with nesterov, dampening 0, wd 0
+//                buf = buf*m + g (two roundings: mul_ then add_)
+//                u   = fma(buf, m, g)   (grad.add(buf, alpha=m): CPU fmadd)
+//                θ   = fma(u, -lr, θ)   (param.add_(grad, alpha=-lr))
+//   copy-back  : inner = θ                              (src/utils.py:226)
 // a3+a4+a5 fused. MODE 0: momentum 0; 1: first step (buf = g); 2: buf = buf*m + g.
 template <int MODE>
 __device__ __forceinline__ void sgd1(float g, float& buf, float& th, const SgdArgs& a) {
@@ -208,9 +187,24 @@ __device__ __forceinline__ void sgd1(float g, float& buf, float& th, const SgdAr
   }
 }
 
-// One element of torch's _single_tensor_adamw (dl_adamw.hip has the formula): contract off, so
-// every operation but the two explicit fmas rounds on its own; sqrt and both divisions are
-// correctly rounded (the Makefile's flags).
+template <int MODE>
+__device__ __forceinline__ void sgd4(const float4& g, float4& buf, float4& th, const SgdArgs& a) {
+  sgd1<MODE>(g.x, buf.x, th.x, a);
+  sgd1<MODE>(g.y, buf.y, th.y, a);
+  sgd1<MODE>(g.z, buf.z, th.z, a);
+  sgd1<MODE>(g.w, buf.w, th.w, a);
+}
+
+// One element of torch's _single_tensor_adamw, every operation rounded on
+// its own except the two explicit fmas; the host hands in the scalars narrowed to fp32 once:
+//   g   = wire / divisor               (IEEE division; divisor 1: untouched)
+//   θ   = θ * decay                    (decay = 1 - lr*wd)
+//   m   = fma(w1, g - m, m)            (exp_avg.lerp_(g, 1 - β1), β1 > 0.5)
+//   v   = v * β2; v = fma(w2 * g, g, v)  (exp_avg_sq.mul_(β2).addcmul_(g, g, value=1 - β2))
+//   den = sqrt(v) / bs + eps           (bs = sqrt(1 - β2^t); correctly rounded sqrt, division)
+//   θ   = θ + (nss * m) / den          (nss = -(lr / (1 - β1^t)); addcdiv_)
+// A zero state (m = v = 0) is the first step: there is no separate first-step body.
+// Contract off; sqrt and both divisions are correctly rounded (the Makefile's flags).
 __device__ __forceinline__ void adam1(float g, float& m, float& v, float& th, const AdamArgs& a) {
   th = th * a.decay;
   m = __builtin_fmaf(a.w1, g - m, m);
@@ -223,7 +217,7 @@ __device__ __forceinline__ void adam1(float g, float& m, float& v, float& th, co
 template <class Body, bool NTL, int NTS>
 hipError_t launch_walk(const Launch& L, const Body& body, int32_t grid) {
   hipLaunchKernelGGL((k_walk<Body, NTL, NTS>), dim3(grid), dim3(kThreads), 0, L.stream, L.chunks,
-                     L.c0, L.c1, L.caddr, L.nchunk, L.xlog, body);
+                     L.c0, L.c1, L.caddr, L.nchunk, body);
   return hipGetLastError();
 }
 

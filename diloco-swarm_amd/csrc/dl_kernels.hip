@@ -8,16 +8,16 @@
 // Default launch: one workgroup per chunk (T125: 30,458 workgroups, ~119 per CU) with
 // non-temporal loads -- the fastest shape measured (tools/hbm_bench.hip).
 //
-// Numerics follow the reference exactly (compiled with -ffp-contract=off and correctly
-// rounded fp32 division):
-//   delta      : outer - inner                         (src/utils.py:221)
-//   average    : sum / n, IEEE true division            (src/comm.py:123)
-//   SGD        : torch _single_tensor_sgd as used with nesterov, dampening 0, wd 0
-//                buf = buf*m + g (two roundings: mul_ then add_)
-//                u   = fma(buf, m, g)   (grad.add(buf, alpha=m): CPU fmadd)
-//                θ   = fma(u, -lr, θ)   (param.add_(grad, alpha=-lr))
-//   copy-back  : inner = θ                              (src/utils.py:226)
-#include "dl_device.h"
+// The outer-step kernels are instantiations of the one body of dl_outer_step.h, gradient
+// source x update rule (the numerics, bit-exact against the reference: beside sgd1, dl_device.h):
+//   dl_unpack_sgd      FromWire x SgdRule             a3 /n + a4 + a5: reads wire, θ, buf
+//   dl_shard_sgd       the same body over a flat shard (k_flat below)
+//   dl_delta_sgd       FromDelta x SgdRule            a2 + a4 + a5 at one peer: 24 B/param (20
+//                      on the first step) instead of 12 + 24 for dl_delta_pack + dl_unpack_sgd
+//   dl_delta_pack_sgd  FromDeltaKeptOnWire x SgdRule  dl_delta_sgd that also stores the packed
+//                      wire: 28 B/param (fp32 wire; 24 first step), wire and θ not read back
+// (dl_adamw.hip: the same sources x AdamRule). The bodies in this file move data only.
+#include "dl_outer_step.h"
 
 namespace dl {
 namespace {
@@ -151,241 +151,6 @@ struct UnpackAvg {
       for (int i = tid; i < ck.len; i += kThreads) {
         const float g = WireIO<W>::ld1(w, i);
         dst[i] = DIV ? g / d : g;
-      }
-    }
-  }
-};
-
-template <typename W, bool DIV, int MODE>
-struct UnpackSgd {
-  const W* wire;
-  float* outer;
-  float* mom;
-  float d;
-  SgdArgs a;
-  int inner_slot;
-  template <bool NTL, int NTS>
-  __device__ __forceinline__ void run(const Chunk& ck, int c, void* const* caddr, int nchunk, int tid) const {
-    float* in = inner_slot >= 0 ? slot_ptr<float>(caddr, nchunk, inner_slot, c) : nullptr;
-    const W* w = wire + ck.poff;
-    float* th = outer + ck.poff;
-    float* mb = mom + ck.poff;
-    if (in == nullptr || aligned16(in)) {
-      const int nv = ck.len >> 2;
-      float4 g[kUnroll], t[kUnroll], m[kUnroll];
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int v = u * kThreads + tid;
-        if (v < nv) {
-          g[u] = WireIO<W>::template ld4<NTL>(w, v);
-          t[u] = ldf4<NTL>(th, v);
-          if (MODE == 2) m[u] = ldf4<NTL>(mb, v);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const float4 gg = DIV ? div4(g[u], d) : g[u];
-        sgd1<MODE>(gg.x, m[u].x, t[u].x, a);
-        sgd1<MODE>(gg.y, m[u].y, t[u].y, a);
-        sgd1<MODE>(gg.z, m[u].z, t[u].z, a);
-        sgd1<MODE>(gg.w, m[u].w, t[u].w, a);
-      }
-      store_rows<NTS>(th, t, nv, tid);
-      if (MODE != 0) store_rows<NTS>(mb, m, nv, tid);
-      if (in) store_rows<NTS>(in, t, nv, tid);
-      const int i = (nv << 2) + tid;
-      if (i < ck.len) {
-        float gg = WireIO<W>::ld1(w, i);
-        if (DIV) gg = gg / d;
-        float b = (MODE == 2) ? mb[i] : 0.f, t1 = th[i];
-        sgd1<MODE>(gg, b, t1, a);
-        th[i] = t1;
-        if (MODE != 0) mb[i] = b;
-        if (in) in[i] = t1;
-      }
-    } else {
-      for (int i = tid; i < ck.len; i += kThreads) {
-        float gg = WireIO<W>::ld1(w, i);
-        if (DIV) gg = gg / d;
-        float b = (MODE == 2) ? mb[i] : 0.f, t1 = th[i];
-        sgd1<MODE>(gg, b, t1, a);
-        th[i] = t1;
-        if (MODE != 0) mb[i] = b;
-        in[i] = t1;
-      }
-    }
-  }
-};
-
-// a2+a4+a5 at ONE peer (src/comm.py:118-119: no all-reduce, no division): the delta never
-// leaves registers. g = θ - inner; SGD; θ and inner <- θ'. 24 B/param (20 first step)
-// instead of 12 + 24 for delta_pack + unpack_sgd; results are bit-identical to that pair.
-template <int MODE>
-struct DeltaSgd {
-  float* outer;
-  float* mom;
-  SgdArgs a;
-  int inner_slot;
-  template <bool NTL, int NTS>
-  __device__ __forceinline__ void run(const Chunk& ck, int c, void* const* caddr, int nchunk, int tid) const {
-    float* in = slot_ptr<float>(caddr, nchunk, inner_slot, c);
-    float* th = outer + ck.poff;
-    float* mb = mom + ck.poff;
-    if (aligned16(in)) {
-      const int nv = ck.len >> 2;
-      float4 x[kUnroll], t[kUnroll], m[kUnroll];
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int v = u * kThreads + tid;
-        if (v < nv) {
-          t[u] = ldf4<NTL>(th, v);
-          x[u] = ldf4<NTL>(in, v);
-          if (MODE == 2) m[u] = ldf4<NTL>(mb, v);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const float4 g = sub4(t[u], x[u]);
-        sgd1<MODE>(g.x, m[u].x, t[u].x, a);
-        sgd1<MODE>(g.y, m[u].y, t[u].y, a);
-        sgd1<MODE>(g.z, m[u].z, t[u].z, a);
-        sgd1<MODE>(g.w, m[u].w, t[u].w, a);
-      }
-      store_rows<NTS>(th, t, nv, tid);
-      if (MODE != 0) store_rows<NTS>(mb, m, nv, tid);
-      store_rows<NTS>(in, t, nv, tid);
-      const int i = (nv << 2) + tid;
-      if (i < ck.len) {
-        const float g = th[i] - in[i];
-        float b = (MODE == 2) ? mb[i] : 0.f, t1 = th[i];
-        sgd1<MODE>(g, b, t1, a);
-        th[i] = t1;
-        if (MODE != 0) mb[i] = b;
-        in[i] = t1;
-      }
-    } else {
-      for (int i = tid; i < ck.len; i += kThreads) {
-        const float g = th[i] - in[i];
-        float b = (MODE == 2) ? mb[i] : 0.f, t1 = th[i];
-        sgd1<MODE>(g, b, t1, a);
-        th[i] = t1;
-        if (MODE != 0) mb[i] = b;
-        in[i] = t1;
-      }
-    }
-  }
-};
-
-// a2+a3+a4+a5 at ONE peer with the pseudo-gradient kept: dl_delta_sgd that also stores the
-// packed wire (outer.grad of src/utils.py:221, the reference's observable .grad after the
-// step). g = θ - inner; wire = W(g); the SGD consumes the value on the wire (a bf16 wire
-// rounds it first, as dl_unpack_sgd would read it back); θ, buf, inner <- new values.
-// 28 B/param (fp32 wire; 24 on the first step) instead of 12 + 24 for dl_delta_pack +
-// dl_unpack_sgd: the wire and θ are not read back. Bit-identical to that pair.
-template <typename W, int MODE>
-struct DeltaPackSgd {
-  float* outer;
-  W* wire;
-  float* mom;
-  SgdArgs a;
-  int inner_slot;
-  static __device__ __forceinline__ float on_wire(float g) {
-    if constexpr (sizeof(W) == 2) return bf2f(f2bf(g));
-    else return g;
-  }
-  template <bool NTL, int NTS>
-  __device__ __forceinline__ void run(const Chunk& ck, int c, void* const* caddr, int nchunk, int tid) const {
-    float* in = slot_ptr<float>(caddr, nchunk, inner_slot, c);
-    float* th = outer + ck.poff;
-    float* mb = mom + ck.poff;
-    W* w = wire + ck.poff;
-    if (aligned16(in)) {
-      const int nv = ck.len >> 2;
-      float4 x[kUnroll], t[kUnroll], m[kUnroll];
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int v = u * kThreads + tid;
-        if (v < nv) {
-          t[u] = ldf4<NTL>(th, v);
-          x[u] = ldf4<NTL>(in, v);
-          if (MODE == 2) m[u] = ldf4<NTL>(mb, v);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) x[u] = sub4(t[u], x[u]);  // the pseudo-gradient
-      // Store order of the four output streams (DL_DPS_ORDER, tools/store_order_ab.py; the
-      // product build is 0): 0 = the SGD arithmetic, then wire, θ, momentum, inner, each
-      // stream's rows back to back; 1 = the wire rows issued before the SGD arithmetic;
-      // 2 = row by row across the four streams; 3 = inner, momentum, θ, wire.
-#if DL_DPS_ORDER == 1
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int v = u * kThreads + tid;
-        if (v < nv) WireIO<W>::template st4<DL_DPS_WIRE_NTS(NTS)>(w, v, x[u]);
-      }
-#endif
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const float4 g = make_float4(on_wire(x[u].x), on_wire(x[u].y), on_wire(x[u].z),
-                                     on_wire(x[u].w));
-        sgd1<MODE>(g.x, m[u].x, t[u].x, a);
-        sgd1<MODE>(g.y, m[u].y, t[u].y, a);
-        sgd1<MODE>(g.z, m[u].z, t[u].z, a);
-        sgd1<MODE>(g.w, m[u].w, t[u].w, a);
-      }
-#if DL_DPS_ORDER == 2
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int v = u * kThreads + tid;
-        if (v < nv) {
-          WireIO<W>::template st4<DL_DPS_WIRE_NTS(NTS)>(w, v, x[u]);
-          stf4<NTS>(th, v, t[u]);
-          if (MODE != 0) stf4<NTS>(mb, v, m[u]);
-          stf4<NTS>(in, v, t[u]);
-        }
-      }
-#elif DL_DPS_ORDER == 3
-      store_rows<NTS>(in, t, nv, tid);
-      if (MODE != 0) store_rows<NTS>(mb, m, nv, tid);
-      store_rows<NTS>(th, t, nv, tid);
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int v = u * kThreads + tid;
-        if (v < nv) WireIO<W>::template st4<DL_DPS_WIRE_NTS(NTS)>(w, v, x[u]);
-      }
-#else
-#if DL_DPS_ORDER == 0
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int v = u * kThreads + tid;
-        if (v < nv) WireIO<W>::template st4<DL_DPS_WIRE_NTS(NTS)>(w, v, x[u]);
-      }
-#endif
-      store_rows<NTS>(th, t, nv, tid);
-      if (MODE != 0) store_rows<NTS>(mb, m, nv, tid);
-      store_rows<NTS>(in, t, nv, tid);
-#endif
-      const int i = (nv << 2) + tid;
-      if (i < ck.len) {
-        const float g0 = th[i] - in[i];
-        WireIO<W>::st1(w, i, g0);
-        const float g = on_wire(g0);
-        float b = (MODE == 2) ? mb[i] : 0.f, t1 = th[i];
-        sgd1<MODE>(g, b, t1, a);
-        th[i] = t1;
-        if (MODE != 0) mb[i] = b;
-        in[i] = t1;
-      }
-    } else {
-      for (int i = tid; i < ck.len; i += kThreads) {
-        const float g0 = th[i] - in[i];
-        WireIO<W>::st1(w, i, g0);
-        const float g = on_wire(g0);
-        float b = (MODE == 2) ? mb[i] : 0.f, t1 = th[i];
-        sgd1<MODE>(g, b, t1, a);
-        th[i] = t1;
-        if (MODE != 0) mb[i] = b;
-        in[i] = t1;
       }
     }
   }
@@ -746,31 +511,17 @@ hipError_t launch_unpack_avg(const Launch& L, const void* wire, int wire_dtype, 
   return unpack_avg_t(L, static_cast<const float*>(wire), divisor, dst_slot, dst_packed);
 }
 
-template <typename W, bool DIV>
-static hipError_t unpack_sgd_mode(const Launch& L, const W* w, float d, float* outer, float* mom,
-                                  SgdArgs a, int inner_slot) {
-  if (a.momentum == 0.f) return run(L, UnpackSgd<W, DIV, 0>{w, outer, mom, d, a, inner_slot});
-  if (a.first) return run(L, UnpackSgd<W, DIV, 1>{w, outer, mom, d, a, inner_slot});
-  return run(L, UnpackSgd<W, DIV, 2>{w, outer, mom, d, a, inner_slot});
-}
-
-template <typename W>
-static hipError_t unpack_sgd_t(const Launch& L, const W* w, int divisor, float* outer, float* mom,
-                               SgdArgs a, int inner_slot) {
-  const float d = float(divisor);
-  if (divisor == 1) return unpack_sgd_mode<W, false>(L, w, d, outer, mom, a, inner_slot);
-  return unpack_sgd_mode<W, true>(L, w, d, outer, mom, a, inner_slot);
-}
-
 hipError_t launch_unpack_sgd(const Launch& L, const void* wire, int wire_dtype, int divisor,
                              float* outer, float* mom, SgdArgs a, int inner_slot) {
-  if (wire_dtype == DL_BF16)
-    return unpack_sgd_t(L, static_cast<const bf16_t*>(wire), divisor, outer, mom, a, inner_slot);
-  return unpack_sgd_t(L, static_cast<const float*>(wire), divisor, outer, mom, a, inner_slot);
+  return with_wire(wire, wire_dtype, divisor, [&](auto grad) {
+    return with_sgd_rule(mom, a, [&](auto rule) {
+      return run(L, outer_step(outer, grad, rule, inner_slot));
+    });
+  });
 }
 
 // Sharded outer step: after the reduce-scatter each peer owns a contiguous 1/n of
-// every bucket; the same UnpackSgd body runs over it as flat 4096-element chunks (no tree, no
+// every bucket; dl_unpack_sgd's body runs over it as flat 4096-element chunks (no tree, no
 // inner copy: θ is all-gathered and scattered to the inner params afterwards).
 template <class Body>
 __global__ void __launch_bounds__(kThreads) k_flat(int64_t n, Body body) {
@@ -780,7 +531,7 @@ __global__ void __launch_bounds__(kThreads) k_flat(int64_t n, Body body) {
     ck.poff = base;
     ck.len = int32_t(n - base < DL_CHUNK_ELEMS ? n - base : DL_CHUNK_ELEMS);
     ck.seg = 0;
-    body.template run<true, true>(ck, 0, nullptr, 0, int(threadIdx.x));  // NT loads + stores
+    body.template run<true, kStNT>(ck, 0, nullptr, 0, int(threadIdx.x));  // NT loads + stores
   }
 }
 
@@ -791,27 +542,13 @@ static hipError_t run_flat(int64_t n, const Body& body, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <typename W, bool DIV>
-static hipError_t shard_sgd_mode(const W* w, float d, float* outer, float* mom, int64_t n,
-                                 SgdArgs a, hipStream_t s) {
-  if (a.momentum == 0.f) return run_flat(n, UnpackSgd<W, DIV, 0>{w, outer, mom, d, a, -1}, s);
-  if (a.first) return run_flat(n, UnpackSgd<W, DIV, 1>{w, outer, mom, d, a, -1}, s);
-  return run_flat(n, UnpackSgd<W, DIV, 2>{w, outer, mom, d, a, -1}, s);
-}
-
-template <typename W>
-static hipError_t shard_sgd_t(const W* w, int divisor, float* outer, float* mom, int64_t n,
-                              SgdArgs a, hipStream_t s) {
-  const float d = float(divisor);
-  if (divisor == 1) return shard_sgd_mode<W, false>(w, d, outer, mom, n, a, s);
-  return shard_sgd_mode<W, true>(w, d, outer, mom, n, a, s);
-}
-
 hipError_t launch_shard_sgd(const void* wire, int wire_dtype, int divisor, float* outer, float* mom,
                             int64_t n, SgdArgs a, hipStream_t s) {
-  if (wire_dtype == DL_BF16)
-    return shard_sgd_t(static_cast<const bf16_t*>(wire), divisor, outer, mom, n, a, s);
-  return shard_sgd_t(static_cast<const float*>(wire), divisor, outer, mom, n, a, s);
+  return with_wire(wire, wire_dtype, divisor, [&](auto grad) {
+    return with_sgd_rule(mom, a, [&](auto rule) {
+      return run_flat(n, outer_step(outer, grad, rule, -1), s);
+    });
+  });
 }
 
 // a3 + a4 after an all_to_all (OuterSync(exchange="a2a"), the deterministic alternative to a
@@ -881,10 +618,7 @@ __global__ void __launch_bounds__(kThreads)
         if constexpr (MODE == 3) {
           stf4<kStNT>(t0, v, gg);
         } else {
-          sgd1<MODE>(gg.x, m[u].x, t[u].x, a);
-          sgd1<MODE>(gg.y, m[u].y, t[u].y, a);
-          sgd1<MODE>(gg.z, m[u].z, t[u].z, a);
-          sgd1<MODE>(gg.w, m[u].w, t[u].w, a);
+          sgd4<MODE>(gg, m[u], t[u], a);
           stf4<kStNT>(t0, v, t[u]);
           if (MODE != 0) stf4<kStNT>(m0, v, m[u]);
         }
@@ -936,24 +670,18 @@ hipError_t launch_slices_sgd(const void* slices, int wire_dtype, int32_t n, int6
 }
 
 hipError_t launch_delta_sgd(const Launch& L, int inner_slot, float* outer, float* mom, SgdArgs a) {
-  if (a.momentum == 0.f) return run(L, DeltaSgd<0>{outer, mom, a, inner_slot});
-  if (a.first) return run(L, DeltaSgd<1>{outer, mom, a, inner_slot});
-  return run(L, DeltaSgd<2>{outer, mom, a, inner_slot});
-}
-
-template <typename W>
-static hipError_t delta_pack_sgd_t(const Launch& L, int inner_slot, float* outer, W* wire,
-                                   float* mom, SgdArgs a) {
-  if (a.momentum == 0.f) return run(L, DeltaPackSgd<W, 0>{outer, wire, mom, a, inner_slot});
-  if (a.first) return run(L, DeltaPackSgd<W, 1>{outer, wire, mom, a, inner_slot});
-  return run(L, DeltaPackSgd<W, 2>{outer, wire, mom, a, inner_slot});
+  return with_sgd_rule(mom, a, [&](auto rule) {
+    return run(L, outer_step(outer, FromDelta{}, rule, inner_slot));
+  });
 }
 
 hipError_t launch_delta_pack_sgd(const Launch& L, int inner_slot, float* outer, void* wire,
                                  int wire_dtype, float* mom, SgdArgs a) {
-  if (wire_dtype == DL_BF16)
-    return delta_pack_sgd_t(L, inner_slot, outer, static_cast<bf16_t*>(wire), mom, a);
-  return delta_pack_sgd_t(L, inner_slot, outer, static_cast<float*>(wire), mom, a);
+  return with_kept_wire(wire, wire_dtype, [&](auto grad) {
+    return with_sgd_rule(mom, a, [&](auto rule) {
+      return run(L, outer_step(outer, grad, rule, inner_slot));
+    });
+  });
 }
 
 hipError_t launch_gather(const Launch& L, int src_slot, void* packed, int dtype) {

@@ -166,6 +166,14 @@ struct UnpackSgdQ8 {
     const float s = *reinterpret_cast<const float*>(slot);
     float* th = outer + ck.poff;
     float* mb = mom + ck.poff;
+    auto one = [&](int i) {
+      const float g = float(int8_t(q[i])) * s;
+      float b = (MODE == 2) ? mb[i] : 0.f, t1 = th[i];
+      sgd1<MODE>(g, b, t1, a);
+      th[i] = t1;
+      if (MODE != 0) mb[i] = b;
+      if (in) in[i] = t1;
+    };
     if (in == nullptr || aligned16(in)) {
       const int nv = ck.len >> 2;
       uint32_t w[kUnroll];
@@ -192,34 +200,16 @@ struct UnpackSgdQ8 {
       for (int u = 0; u < kUnroll; ++u) {
         const int v = u * kThreads + tid;
         if (v < nv) {
-          const float4 g = unpack4(w[u], s);
-          sgd1<MODE>(g.x, m[u].x, t[u].x, a);
-          sgd1<MODE>(g.y, m[u].y, t[u].y, a);
-          sgd1<MODE>(g.z, m[u].z, t[u].z, a);
-          sgd1<MODE>(g.w, m[u].w, t[u].w, a);
+          sgd4<MODE>(unpack4(w[u], s), m[u], t[u], a);
           stf4<NTS>(th, v, t[u]);
           if (MODE != 0) stf4<NTS>(mb, v, m[u]);
           if (in) stf4<NTS>(in, v, t[u]);
         }
       }
       const int i = (nv << 2) + tid;
-      if (i < ck.len) {
-        const float g = float(int8_t(q[i])) * s;
-        float b = (MODE == 2) ? mb[i] : 0.f, t1 = th[i];
-        sgd1<MODE>(g, b, t1, a);
-        th[i] = t1;
-        if (MODE != 0) mb[i] = b;
-        if (in) in[i] = t1;
-      }
+      if (i < ck.len) one(i);
     } else {
-      for (int i = tid; i < ck.len; i += kThreads) {
-        const float g = float(int8_t(q[i])) * s;
-        float b = (MODE == 2) ? mb[i] : 0.f, t1 = th[i];
-        sgd1<MODE>(g, b, t1, a);
-        th[i] = t1;
-        if (MODE != 0) mb[i] = b;
-        in[i] = t1;
-      }
+      for (int i = tid; i < ck.len; i += kThreads) one(i);
     }
   }
 };

@@ -52,22 +52,9 @@ __global__ void __launch_bounds__(kThreads)
           g = make_float4(g.x + d.x, g.y + d.y, g.z + d.z, g.w + d.w);
         }
         if (N > 1) g = div4(g, float(N));
-        if (mode == 0) {
-          sgd1<0>(g.x, m[u].x, t[u].x, a);
-          sgd1<0>(g.y, m[u].y, t[u].y, a);
-          sgd1<0>(g.z, m[u].z, t[u].z, a);
-          sgd1<0>(g.w, m[u].w, t[u].w, a);
-        } else if (mode == 1) {
-          sgd1<1>(g.x, m[u].x, t[u].x, a);
-          sgd1<1>(g.y, m[u].y, t[u].y, a);
-          sgd1<1>(g.z, m[u].z, t[u].z, a);
-          sgd1<1>(g.w, m[u].w, t[u].w, a);
-        } else {
-          sgd1<2>(g.x, m[u].x, t[u].x, a);
-          sgd1<2>(g.y, m[u].y, t[u].y, a);
-          sgd1<2>(g.z, m[u].z, t[u].z, a);
-          sgd1<2>(g.w, m[u].w, t[u].w, a);
-        }
+        if (mode == 0) sgd4<0>(g, m[u], t[u], a);
+        else if (mode == 1) sgd4<1>(g, m[u], t[u], a);
+        else sgd4<2>(g, m[u], t[u], a);
         if (mode != 0) stf4<true>(mom + base, u * kThreads + threadIdx.x, m[u]);
 #pragma unroll
         for (int q = 0; q < N; ++q) stf4<true>(p.theta[q] + k0, u * kThreads + threadIdx.x, t[u]);

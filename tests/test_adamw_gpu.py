@@ -1,5 +1,6 @@
 """The fused AdamW outer step on the GPU: dl_unpack_adamw and dl_delta_pack_adamw against the
-numpy restatement of their contract (tests/adamw_restatement.py) on a ragged tree, and the
+numpy restatement of their contract (tests/adamw_restatement.py) on a ragged tree (and, beside
+it, dl_unpack_sgd -- the same walker body with the SGD rule -- against the CPU oracle), and the
 reference's four calls with DILOCO_OUTER_ADAMW=fused at one peer and over two gloo processes
 on the one GPU (RCCL refuses two ranks on one device; the kernels are the product's)."""
 import os
@@ -19,6 +20,7 @@ from diloco_amd import _lib, synth
 from diloco_amd.kernels import HipKernels, adamw_scalars, set_default_kernels
 from diloco_amd.plan import SLOT_INNER, PackedTree
 from diloco_amd.trees import get_tree
+from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -134,6 +136,49 @@ def test_unpack_adamw_matches_the_restatement(misaligned, wire, divisor, bound):
         _eq(p.get(p.wire), g, ("wire", s))
         _eq([x.cpu().numpy() for x in inner], th if bound else inner0, ("inner", s))
         assert p.padding_is_zero(p.theta, p.m, p.v, p.wire)
+    p.tree.close()
+
+
+@pytest.mark.parametrize("momentum,nesterov", [(0.9, True), (0.9, False), (0.0, False)])
+@pytest.mark.parametrize("divisor", [1, 3])
+@pytest.mark.parametrize("wire", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("inner", ["aligned", "misaligned", "unbound"])
+def test_unpack_sgd_matches_the_oracle(inner, wire, divisor, momentum, nesterov):
+    """The SGD twin: dl_unpack_sgd called directly, bucket by bucket on the ragged tree, one
+    first and one steady step: θ, the momentum buffer and the inner tensors (inner_slot -1:
+    untouched) byte-equal to the CPU oracle's division and SGD; the wire is only read; padding
+    stays zero. Without a momentum the buffer is not passed and stays as it was."""
+    rng = np.random.default_rng(29)
+    th = [rng.standard_normal(n).astype(F) for n in RAGGED]
+    buf = [np.zeros(n, F) for n in RAGGED]
+    p = _Packed(wire)
+    p.put(p.theta, th)
+    inner0 = [rng.standard_normal(n).astype(F) for n in RAGGED]
+    tensors = _inner_tensors(inner0, inner == "misaligned")
+    p.bind_inner(tensors)
+    slot = -1 if inner == "unbound" else SLOT_INNER
+    stream = torch.cuda.current_stream().cuda_stream
+    for first in (True, False):
+        g = _grads(rng, divisor)
+        if wire == torch.bfloat16:
+            g = [bf16_round(x) for x in g]
+        p.put(p.wire, g)
+        for b in range(p.tree.n_buckets):
+            _lib.call("dl_unpack_sgd", p.tree.handle, b, p.wire.data_ptr(),
+                      _lib.DL_BF16 if wire == torch.bfloat16 else _lib.DL_F32, divisor,
+                      p.theta.data_ptr(), p.m.data_ptr() if momentum else None, 0.7, momentum,
+                      int(nesterov), int(first), slot, stream)
+        torch.cuda.synchronize()
+        for t, n in enumerate(RAGGED):
+            gg = g[t] if divisor == 1 else (g[t] / F(divisor)).astype(F)
+            if n:
+                oracle.sgd(th[t], buf[t] if momentum else None, gg, 0.7, momentum, nesterov, first)
+        _eq(p.get(p.theta), th, ("theta", first))
+        _eq(p.get(p.m), buf, ("momentum", first))
+        _eq(p.get(p.wire), g, ("wire", first))
+        _eq([x.cpu().numpy() for x in tensors], inner0 if inner == "unbound" else th,
+            ("inner", first))
+        assert p.padding_is_zero(p.theta, p.m, p.wire)
     p.tree.close()
 
 

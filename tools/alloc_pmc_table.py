@@ -10,14 +10,18 @@ import sys
 from collections import defaultdict
 
 
+def _is_dps(name):  # dl_delta_pack_sgd: the outer-step body, delta kept on the wire, SGD rule
+    return "FromDeltaKeptOnWire" in name and "SgdRule" in name
+
+
 def table(d):
     dur = {}
     for r in csv.DictReader(open(os.path.join(d, "run_kernel_trace.csv"))):
-        if "DeltaPackSgd" in r["Kernel_Name"]:
+        if _is_dps(r["Kernel_Name"]):
             dur[int(r["Dispatch_Id"])] = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
     cnt = defaultdict(dict)
     for r in csv.DictReader(open(os.path.join(d, "run_counter_collection.csv"))):
-        if "DeltaPackSgd" in r["Kernel_Name"]:
+        if _is_dps(r["Kernel_Name"]):
             cnt[int(r["Dispatch_Id"])][r["Counter_Name"]] = float(r["Counter_Value"])
     ids = sorted(cnt)
     names = sorted(next(iter(cnt.values())))

@@ -17,12 +17,21 @@ from collections import defaultdict
 
 
 def short(name):
-    # most specific first: k_flat<UnpackSgd...> is dl_shard_sgd, UnpackSgdQ8 is not UnpackSgd
-    names = {"k_xgmi_reduce_sgd": "xgmi_reduce_sgd", "k_flat": "shard_sgd", "DeltaQ8": "delta_q8", "UnpackSgdQ8": "unpack_sgd_q8",
-             "k_q8_reduce": "q8_reduce", "DeltaPackSgd": "delta_pack_sgd",
+    # the outer-step body (csrc/dl_outer_step.h): OuterStep<gradient source, update rule> under
+    # k_walk, or under k_flat for dl_shard_sgd; SgdRule's MODE 1 is the first step
+    m = re.search(r"OuterStep<.*?\b(FromWire|FromDeltaKeptOnWire|FromDelta)\b.*?"
+                  r"\b(AdamRule|SgdRule<(\d)>)", name)
+    if m:
+        src = {"FromWire": "unpack", "FromDelta": "delta", "FromDeltaKeptOnWire": "delta_pack"}
+        v = "shard_sgd" if "k_flat" in name else src[m.group(1)] + (
+            "_adamw" if m.group(2) == "AdamRule" else "_sgd")
+        return v + ("_first" if m.group(3) == "1" else "")
+    # most specific first: UnpackSgdQ8 before the plain bodies, DeltaPackPair before DeltaPack
+    names = {"k_xgmi_reduce_sgd": "xgmi_reduce_sgd", "DeltaQ8": "delta_q8", "UnpackSgdQ8": "unpack_sgd_q8",
+             "k_q8_reduce": "q8_reduce",
              "DeltaPackPair": "delta_pack_pairs", "GatherPair": "gather_pairs",
-             "DeltaPack": "delta_pack", "UnpackSgd": "unpack_sgd",
-             "UnpackAvg": "unpack_avg", "DeltaSgd": "delta_sgd", "Gather": "gather",
+             "DeltaPack": "delta_pack",
+             "UnpackAvg": "unpack_avg", "Gather": "gather",
              "Scatter": "scatter", "k_fill_synth": "fill_synth",
              "k_serialize_f32x4": "serialize_f32", "k_serialize<unsigned short>": "serialize_bf16",
              "k_slices_sgd": "shard_reduce_sgd"}
@@ -30,12 +39,10 @@ def short(name):
         return "xgmi_delta_sgd"  # the pack-free variant (exchange="xgmi_inner")
     for k, v in names.items():
         if k in name:
-            # the SGD bodies' MODE (1 = first step) is the last argument of the body's own
+            # these SGD kernels' MODE (1 = first step) is the last argument of their own
             # template list (k_walk's trailing arguments are the load / store policy)
-            body = "UnpackSgd" if k == "k_flat" else k
-            m = re.search(re.escape(body) + r"<([^<>]*)>", name)
-            first = (k in ("UnpackSgd", "k_flat", "DeltaSgd", "DeltaPackSgd", "UnpackSgdQ8",
-                           "k_slices_sgd")
+            m = re.search(re.escape(k) + r"<([^<>]*)>", name)
+            first = (k in ("UnpackSgdQ8", "k_slices_sgd")
                      and m is not None and m.group(1).split(",")[-1].strip() == "1")
             if k == "k_slices_sgd" and m is not None:  # the slice count is its first argument
                 nsl = m.group(1).split(",")[0].strip()
