@@ -548,6 +548,40 @@ DL_API int dl_delta_pack_sgd(dl_tree_t t, int32_t b, int32_t inner_slot, float* 
   return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_pack_sgd") : hip_fail(e, "dl_delta_pack_sgd");
 }
 
+DL_API int dl_delta_pack_sgd_defer(dl_tree_t t, int32_t b, int32_t inner_slot, float* outer,
+                                   float* wire, float* mom, float lr, float momentum,
+                                   int32_t nesterov, int32_t first_step, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_delta_pack_sgd_defer", kAutoUnpackSgd));
+  DL_TRY(check_slot(t, inner_slot, "dl_delta_pack_sgd_defer"));
+  DL_TRY(check_packed(outer, "dl_delta_pack_sgd_defer", "outer"));
+  DL_TRY(check_packed(wire, "dl_delta_pack_sgd_defer", "wire"));
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_delta_pack_sgd_defer", mom, lr, momentum, nesterov, first_step, &a));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_delta_pack_sgd_defer"));
+  hipError_t e = dl::launch_delta_pack_sgd_defer(L, inner_slot, outer, wire, mom, a);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_pack_sgd_defer") : hip_fail(e, "dl_delta_pack_sgd_defer");
+}
+
+DL_API int dl_delta_pack_sgd_resume(dl_tree_t t, int32_t b, int32_t inner_slot, float* outer,
+                                    float* wire, float* mom, float pending_lr,
+                                    float pending_momentum, int32_t pending_nesterov,
+                                    int32_t pending_first_step, float lr, float momentum,
+                                    int32_t nesterov, int32_t first_step, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_delta_pack_sgd_resume", kAutoUnpackSgd));
+  DL_TRY(check_slot(t, inner_slot, "dl_delta_pack_sgd_resume"));
+  DL_TRY(check_packed(outer, "dl_delta_pack_sgd_resume", "outer"));
+  DL_TRY(check_packed(wire, "dl_delta_pack_sgd_resume", "wire"));
+  dl::SgdArgs p, a;
+  DL_TRY(sgd_args("dl_delta_pack_sgd_resume", mom, pending_lr, pending_momentum, pending_nesterov,
+                  pending_first_step, &p));
+  DL_TRY(sgd_args("dl_delta_pack_sgd_resume", mom, lr, momentum, nesterov, first_step, &a));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_delta_pack_sgd_resume"));
+  hipError_t e = dl::launch_delta_pack_sgd_resume(L, inner_slot, outer, wire, mom, p, a);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_pack_sgd_resume") : hip_fail(e, "dl_delta_pack_sgd_resume");
+}
+
 // The AdamW outer step (dl_adamw.hip). Like the SGD kernels, nothing re-reads what they write
 // next: non-temporal loads and stores.
 DL_API int dl_unpack_adamw(dl_tree_t t, int32_t b, const void* wire, int32_t wire_dtype,

@@ -81,6 +81,12 @@ hipError_t launch_unpack_sgd(const Launch& L, const void* wire, int wire_dtype, 
 hipError_t launch_delta_sgd(const Launch& L, int inner_slot, float* outer, float* mom, SgdArgs a);
 hipError_t launch_delta_pack_sgd(const Launch& L, int inner_slot, float* outer, void* wire,
                                  int wire_dtype, float* mom, SgdArgs a);
+// the same step with θ and the momentum left unstored (fp32 wire), and the step after it, which
+// first redoes the pending one from the wire it left
+hipError_t launch_delta_pack_sgd_defer(const Launch& L, int inner_slot, float* outer, float* wire,
+                                       float* mom, SgdArgs a);
+hipError_t launch_delta_pack_sgd_resume(const Launch& L, int inner_slot, float* outer, float* wire,
+                                        float* mom, SgdArgs pending, SgdArgs a);
 hipError_t launch_shard_sgd(const void* wire, int wire_dtype, int divisor, float* outer, float* mom,
                             int64_t n, SgdArgs a, hipStream_t s);
 hipError_t launch_slices_sgd(const void* slices, int wire_dtype, int32_t n, int64_t len,

@@ -16,6 +16,10 @@
 //                      on the first step) instead of 12 + 24 for dl_delta_pack + dl_unpack_sgd
 //   dl_delta_pack_sgd  FromDeltaKeptOnWire x SgdRule  dl_delta_sgd that also stores the packed
 //                      wire: 28 B/param (fp32 wire; 24 first step), wire and θ not read back
+//   dl_delta_pack_sgd_defer   the same with the kDefer policy: θ and the momentum not stored,
+//                      20 B/param; the step stays pending in (θ, momentum, wire)
+//   dl_delta_pack_sgd_resume  FromDeltaAfterPending x SgdRule: the pending step redone in
+//                      registers, then dl_delta_pack_sgd: 32 B/param for two steps' state
 // (dl_adamw.hip: the same sources x AdamRule). The bodies in this file move data only.
 #include "dl_outer_step.h"
 
@@ -680,6 +684,23 @@ hipError_t launch_delta_pack_sgd(const Launch& L, int inner_slot, float* outer, 
   return with_kept_wire(wire, wire_dtype, [&](auto grad) {
     return with_sgd_rule(mom, a, [&](auto rule) {
       return run(L, outer_step(outer, grad, rule, inner_slot));
+    });
+  });
+}
+
+hipError_t launch_delta_pack_sgd_defer(const Launch& L, int inner_slot, float* outer, float* wire,
+                                       float* mom, SgdArgs a) {
+  return with_sgd_rule(mom, a, [&](auto rule) {
+    return run(L, outer_step<true>(outer, FromDeltaKeptOnWire<float>{wire}, rule, inner_slot));
+  });
+}
+
+hipError_t launch_delta_pack_sgd_resume(const Launch& L, int inner_slot, float* outer, float* wire,
+                                        float* mom, SgdArgs pending, SgdArgs a) {
+  return with_sgd_rule(mom, pending, [&](auto pend) {
+    return with_sgd_rule(mom, a, [&](auto rule) {
+      return run(L, outer_step(outer, FromDeltaAfterPending<decltype(pend)>{wire, pend}, rule,
+                               inner_slot));
     });
   });
 }

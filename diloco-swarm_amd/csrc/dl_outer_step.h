@@ -1,9 +1,12 @@
 // The outer step as ONE walker body, OuterStep<Grad, Rule>, with two axes:
 //   Grad  where a chunk's gradient comes from: the wire (with or without the division by the
-//         peer count), θ - inner, or θ - inner with the wire written and the rule stepping on
-//         the value as the wire holds it;
+//         peer count), θ - inner, θ - inner with the wire written and the rule stepping on
+//         the value as the wire holds it, or that after a pending step whose θ and state were
+//         never stored (they are recomputed from the wire that step left);
 //   Rule  what is done with it: SGD (one state stream, the momentum buffer) or AdamW (two,
 //         exp_avg and exp_avg_sq); the arithmetic is sgd1 / adam1 of dl_device.h.
+// and one policy, kDefer: θ and the state are not stored (the wire and inner are), so the step
+// stays pending: the streams as they were plus the wire determine it.
 // Every outer-step kernel of dl_kernels.hip and dl_adamw.hip is an instantiation, so the fused
 // kernels equal the dl_delta_pack + dl_unpack_* pair bit for bit by construction: the element
 // arithmetic is written once, for the float4 rows, the tail lane and the unaligned loop alike.
@@ -52,11 +55,12 @@ struct AdamRule {
 // ---- gradient sources ----------------------------------------------------------------------
 // kDelta: the stream loaded beside θ is the inner parameter and the raw gradient is θ - inner
 // (otherwise it is the wire's value). kKeepsWire: the raw gradient is stored to the wire.
-// fin: the raw gradient -> the value the rule steps on.
+// kPending: θ and the state as loaded are one step behind; `pend`, the rule of that step, is
+// applied to the wire's old value first. fin: the raw gradient -> the value the rule steps on.
 template <typename W, bool DIV>
 struct FromWire {  // a3: the summed wire / n (DIV false: one peer's own wire, untouched)
   using Wire = W;
-  static constexpr bool kDelta = false, kKeepsWire = false;
+  static constexpr bool kDelta = false, kKeepsWire = false, kPending = false;
   const W* wire;
   float d;
   __device__ __forceinline__ const W* at(int64_t poff) const { return wire + poff; }
@@ -67,7 +71,7 @@ struct FromWire {  // a3: the summed wire / n (DIV false: one peer's own wire, u
 // registers
 struct FromDelta {
   using Wire = float;
-  static constexpr bool kDelta = true, kKeepsWire = false;
+  static constexpr bool kDelta = true, kKeepsWire = false, kPending = false;
   __device__ __forceinline__ const float* at(int64_t) const { return nullptr; }
   __device__ __forceinline__ float fin(float g) const { return g; }
 };
@@ -78,13 +82,27 @@ struct FromDelta {
 template <typename W>
 struct FromDeltaKeptOnWire {
   using Wire = W;
-  static constexpr bool kDelta = true, kKeepsWire = true;
+  static constexpr bool kDelta = true, kKeepsWire = true, kPending = false;
   W* wire;
   __device__ __forceinline__ W* at(int64_t poff) const { return wire + poff; }
   __device__ __forceinline__ float fin(float g) const {
     if constexpr (sizeof(W) == 2) return bf2f(f2bf(g));
     else return g;
   }
+};
+
+// FromDeltaKeptOnWire (fp32 wire) after a step run with kDefer: θ, the state and the wire are
+// loaded, `pend` (that step's rule: the same arithmetic, so the same bits it would have stored)
+// brings θ and the state up to date in registers, then g = θ - inner goes over the old wire in
+// place -- the lane that stores a wire element is the one that loaded it
+template <class Pend>
+struct FromDeltaAfterPending {
+  using Wire = float;
+  static constexpr bool kDelta = true, kKeepsWire = true, kPending = true;
+  float* wire;
+  Pend pend;
+  __device__ __forceinline__ float* at(int64_t poff) const { return wire + poff; }
+  __device__ __forceinline__ float fin(float g) const { return g; }
 };
 
 template <int J>
@@ -95,29 +113,52 @@ __device__ __forceinline__ float& comp(float4& v) {
   else return v.w;
 }
 
+// which state streams a step loads and stores: the rule's, and a pending rule's beside them
+template <class Rule, class Grad>
+struct StateIO {
+  static constexpr bool kLoad = Rule::kLoadState, kStore = Rule::kStoreState;
+};
+template <class Rule, class Pend>
+struct StateIO<Rule, FromDeltaAfterPending<Pend>> {
+  static_assert(Pend::kStates == Rule::kStates, "the pending rule steps the same state streams");
+  static constexpr bool kLoad = Rule::kLoadState || Pend::kLoadState;
+  static constexpr bool kStore = Rule::kStoreState || Pend::kStoreState;
+};
+
 // ---- the body ------------------------------------------------------------------------------
 // Per chunk: every 16-B load up front (gradient stream, θ, states), the subtraction or
 // division, the rule per component, then the stores, one stream's rows back to back: wire, θ,
-// state..., inner (inner_slot -1, wire sources only: no copy-back). The < 4 elements past the
-// last float4 go one per lane; a tensor whose storage is only 4-B aligned goes element-wise.
-template <class Grad, class Rule>
+// state..., inner (inner_slot -1, wire sources only: no copy-back; kDefer: no θ, no state). The
+// < 4 elements past the last float4 go one per lane; a tensor whose storage is only 4-B aligned
+// goes element-wise.
+template <class Grad, class Rule, bool kDefer = false>
 struct OuterStep {
   static constexpr int K = Rule::kStates;
   static constexpr bool kWireFirst = Grad::kKeepsWire && Rule::kWireFirst;
+  static constexpr bool kLoadState = StateIO<Rule, Grad>::kLoad;
+  static constexpr bool kStoreState = StateIO<Rule, Grad>::kStore;
+  static_assert(!(Grad::kPending && kWireFirst), "a pending step's wire is read before it is stored");
+  static_assert(!kDefer || (Grad::kKeepsWire && !Grad::kPending), "a deferred step leaves its wire");
   using WIO = WireIO<typename Grad::Wire>;
   float* outer;
   Grad grad;
   Rule rule;
   int inner_slot;
 
-  // component J of row u
+  // component J of row u (a pending source: g holds inner coming in, the gradient going out,
+  // old the wire as the pending step left it)
   template <int J>
-  __device__ __forceinline__ void step(float4 g, float4 (&s)[K][kUnroll], int u, float4& t) const {
+  __device__ __forceinline__ void step(float4& g, float4 (&s)[K][kUnroll], int u, float4& t,
+                                       float4 old) const {
     float e[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) e[k] = Rule::kLoadState ? comp<J>(s[k][u]) : 0.f;
+    for (int k = 0; k < K; ++k) e[k] = kLoadState ? comp<J>(s[k][u]) : 0.f;
+    if constexpr (Grad::kPending) {
+      grad.pend.apply(comp<J>(old), e, comp<J>(t));  // θ and the state the pending step meant
+      comp<J>(g) = comp<J>(t) - comp<J>(g);          // the pseudo-gradient
+    }
     rule.apply(grad.fin(comp<J>(g)), e, comp<J>(t));
-    if (Rule::kStoreState) {
+    if (kStoreState) {
 #pragma unroll
       for (int k = 0; k < K; ++k) comp<J>(s[k][u]) = e[k];
     }
@@ -135,15 +176,16 @@ struct OuterStep {
 
     auto one = [&](int i) {
       float t = th[i], g;
+      float e[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) e[k] = kLoadState ? sp[k][i] : 0.f;
+      if constexpr (Grad::kPending) grad.pend.apply(WIO::ld1(w, i), e, t);
       if constexpr (Grad::kDelta) g = t - in[i];
       else g = WIO::ld1(w, i);
       if constexpr (Grad::kKeepsWire) WIO::st1(w, i, g);
-      float e[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) e[k] = Rule::kLoadState ? sp[k][i] : 0.f;
       rule.apply(grad.fin(g), e, t);
-      th[i] = t;
-      if (Rule::kStoreState) {
+      if constexpr (!kDefer) th[i] = t;
+      if (kStoreState && !kDefer) {
 #pragma unroll
         for (int k = 0; k < K; ++k) sp[k][i] = e[k];
       }
@@ -152,15 +194,16 @@ struct OuterStep {
 
     if (!copy_back || aligned16(in)) {
       const int nv = ck.len >> 2;
-      float4 x[kUnroll], t[kUnroll], s[K][kUnroll];
+      float4 x[kUnroll], t[kUnroll], s[K][kUnroll], old[kUnroll];
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int v = u * kThreads + tid;
         if (v < nv) {
           if constexpr (!Grad::kDelta) x[u] = WIO::template ld4<NTL>(w, v);
+          if constexpr (Grad::kPending) old[u] = WIO::template ld4<NTL>(w, v);
           t[u] = ldf4<NTL>(th, v);
           if constexpr (Grad::kDelta) x[u] = ldf4<NTL>(in, v);
-          if (Rule::kLoadState) {
+          if (kLoadState) {
 #pragma unroll
             for (int k = 0; k < K; ++k) s[k][u] = ldf4<NTL>(sp[k], v);
           }
@@ -179,11 +222,12 @@ struct OuterStep {
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         if (!Rule::kSkipPastChunk || u * kThreads + tid < nv) {
-          if constexpr (Grad::kDelta && !kWireFirst) x[u] = sub4(t[u], x[u]);  // the pseudo-gradient
-          step<0>(x[u], s, u, t[u]);
-          step<1>(x[u], s, u, t[u]);
-          step<2>(x[u], s, u, t[u]);
-          step<3>(x[u], s, u, t[u]);
+          if constexpr (Grad::kDelta && !kWireFirst && !Grad::kPending)
+            x[u] = sub4(t[u], x[u]);  // the pseudo-gradient
+          step<0>(x[u], s, u, t[u], old[u]);
+          step<1>(x[u], s, u, t[u], old[u]);
+          step<2>(x[u], s, u, t[u], old[u]);
+          step<3>(x[u], s, u, t[u], old[u]);
         }
       }
       if constexpr (Grad::kKeepsWire && !kWireFirst) {
@@ -193,8 +237,8 @@ struct OuterStep {
           if (v < nv) WIO::template st4<NTS>(w, v, x[u]);
         }
       }
-      store_rows<NTS>(th, t, nv, tid);
-      if (Rule::kStoreState) {
+      if constexpr (!kDefer) store_rows<NTS>(th, t, nv, tid);
+      if (kStoreState && !kDefer) {
 #pragma unroll
         for (int k = 0; k < K; ++k) store_rows<NTS>(sp[k], s[k], nv, tid);
       }
@@ -207,8 +251,8 @@ struct OuterStep {
   }
 };
 
-template <class Grad, class Rule>
-OuterStep<Grad, Rule> outer_step(float* outer, Grad grad, Rule rule, int inner_slot) {
+template <bool kDefer = false, class Grad, class Rule>
+OuterStep<Grad, Rule, kDefer> outer_step(float* outer, Grad grad, Rule rule, int inner_slot) {
   return {outer, grad, rule, inner_slot};
 }
 

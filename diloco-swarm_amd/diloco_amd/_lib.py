@@ -63,6 +63,13 @@ SIGNATURES = {
     "dl_delta_pack_sgd": (
         ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _f32, _f32, _i32, _i32, _vp],
     ),
+    "dl_delta_pack_sgd_defer": (
+        ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _vp],
+    ),
+    "dl_delta_pack_sgd_resume": (
+        ctypes.c_int,
+        [_vp, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _f32, _f32, _i32, _i32, _vp],
+    ),
     "dl_unpack_adamw": (
         ctypes.c_int,
         [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32,

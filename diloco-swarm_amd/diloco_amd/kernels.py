@@ -96,6 +96,24 @@ class HipKernels:
                   wire.data_ptr(), wire_code(wire.dtype), _ptr(mom), float(lr), float(momentum),
                   int(nesterov), int(first), _s(theta))
 
+    def delta_pack_sgd_defer(self, tree, bucket, inner_slot, theta, wire, mom, lr, momentum,
+                             nesterov, first) -> None:
+        """delta_pack_sgd (fp32 wire) without the stores of θ and the momentum: the step stays
+        pending in (theta, mom, wire) until unpack_sgd(divisor 1, inner_slot -1) with the same
+        hyper-parameters, or delta_pack_sgd_resume, completes it."""
+        _lib.call("dl_delta_pack_sgd_defer", tree.handle, bucket, inner_slot, theta.data_ptr(),
+                  wire.data_ptr(), _ptr(mom), float(lr), float(momentum), int(nesterov),
+                  int(first), _s(theta))
+
+    def delta_pack_sgd_resume(self, tree, bucket, inner_slot, theta, wire, mom, pending, lr,
+                              momentum, nesterov, first) -> None:
+        """The step after a pending one (pending: its lr, momentum, nesterov, first): that
+        step redone in registers, then delta_pack_sgd; theta, mom, wire and inner stored."""
+        p_lr, p_momentum, p_nesterov, p_first = pending
+        _lib.call("dl_delta_pack_sgd_resume", tree.handle, bucket, inner_slot, theta.data_ptr(),
+                  wire.data_ptr(), _ptr(mom), float(p_lr), float(p_momentum), int(p_nesterov),
+                  int(p_first), float(lr), float(momentum), int(nesterov), int(first), _s(theta))
+
     def unpack_adamw(self, tree, bucket, wire, divisor, theta, exp_avg, exp_avg_sq, scalars,
                      inner_slot) -> None:
         """N > 1: the summed wire / divisor, then one AdamW step on θ, exp_avg, exp_avg_sq

@@ -665,9 +665,17 @@ class DeviceOuterMirror:
         self.tree = self.k.tree(self.numels, self.device, bucket_cap_elems, dp_bucket_align())
         self.offs = [int(o) for o in self.tree.seg_off[:-1]]
         z = dict(dtype=torch.float32, device=self.device)
-        self.d_theta = torch.zeros(self.tree.total, **z)
+        # θ and the momentum: raw arenas behind private names. Only the deferred one-peer step
+        # (sgd_step) touches them directly; everything else goes through d_theta / d_mom, which
+        # complete a pending step first
+        self._theta = torch.zeros(self.tree.total, **z)
         self.d_wire = torch.zeros(self.tree.total, **z)
-        self.d_mom: Optional[torch.Tensor] = None
+        self._mom: Optional[torch.Tensor] = None
+        # the one-peer SGD step stores θ and the momentum only every second step (set by the
+        # lazy host placement, whose HBM twin nobody reads but through its hooks), and the
+        # step whose θ and momentum are still to be stored: (lr, momentum, nesterov, first)
+        self.defer_state = False
+        self._pend: Optional[tuple] = None
         # wire="bf16" (BASELINE config #5 behind the drop-in calls): at N > 1 the deltas cross
         # the wire in bf16 (cast in the pack kernel, RCCL's bf16 SUM) and the SGD pass reads
         # them from it; .grad shows the decoded average (the codec's value, not fp32's)
@@ -680,7 +688,7 @@ class DeviceOuterMirror:
         self._works: Optional[list] = None
         # per-tensor views of each arena and their addresses, made once: the per-step checks
         # compare raw addresses (an outer step must not cost a Python tensor per parameter)
-        self._views = {"theta": self._make_views(self.d_theta),
+        self._views = {"theta": self._make_views(self._theta),
                        "wire": self._make_views(self.d_wire)}
         self._ptrs = {k: [v.data_ptr() for v in vs] for k, vs in self._views.items()}
         # fused mode: OuterParameter flags assignments of .grad / .data, so the address checks
@@ -731,6 +739,34 @@ class DeviceOuterMirror:
         # asked for: its fused step needs the whole averaged wire on every rank (replicated)
         self.adamw_replicated = False
 
+    # ---- the pending one-peer step -------------------------------------------------------
+    def settle_state(self) -> None:
+        """θ and the momentum arenas hold the last step's values. After a deferred step
+        (dl_delta_pack_sgd_defer) they are one step behind and the wire holds that step's
+        pseudo-gradient: dl_unpack_sgd with the step's own scalars stores what it left out,
+        the same bits (one element function, contraction off)."""
+        pend, self._pend = self._pend, None
+        if pend is not None:
+            lr, momentum, nesterov, first = pend
+            self.k.unpack_sgd(self.tree, ALL, self.d_wire, 1, self._theta,
+                              self._mom if momentum != 0 else None, lr, momentum, nesterov,
+                              first, -1)
+
+    @property
+    def d_theta(self) -> torch.Tensor:
+        self.settle_state()
+        return self._theta
+
+    @property
+    def d_mom(self) -> Optional[torch.Tensor]:
+        self.settle_state()
+        return self._mom
+
+    @d_mom.setter
+    def d_mom(self, value) -> None:
+        self.settle_state()
+        self._mom = value
+
     def _momentum_buffer(self, view: torch.Tensor) -> "MomentumBuffer":
         t = view.as_subclass(MomentumBuffer)
         t.__dict__["_dl_mirror"] = weakref.ref(self)
@@ -774,7 +810,7 @@ class DeviceOuterMirror:
     def _theta_version(self):
         """fused: d_theta's version counter, shared by every outer parameter (one integer);
         eager, or parameters kept in place: the parameters' own counters."""
-        return self.d_theta._version if self._shared_ver else _vers(self.params)
+        return self._theta._version if self._shared_ver else _vers(self.params)
 
     def _make_views(self, arena: torch.Tensor) -> List[torch.Tensor]:
         return [arena[o:o + n].view(p.shape)
@@ -801,6 +837,7 @@ class DeviceOuterMirror:
         device: empty tensors' addresses can coincide across devices)."""
         if not force and self._in_place(kind, what):
             return False
+        self.settle_state()  # the arenas are about to be written: a pending step lands first
         views = self._views[kind]
         with torch.no_grad():
             for i, p in enumerate(self.params):
@@ -1024,6 +1061,7 @@ class DeviceOuterMirror:
                    ordered: bool = False) -> None:
         """grad = Σ_peers grad / n (src/comm.py:120-123), in place on the packed .grad.
         ordered (DILOCO_DP_EXCHANGE=a2a): the rank-order sum, bit-exact at every n."""
+        self.settle_state()
         if self.wire == "int8":  # its exchange sums in rank order already (dl_q8_reduce)
             self._all_reduce_q8(group, num_peers)
             return
@@ -1283,10 +1321,12 @@ class DeviceOuterMirror:
             self._relay_grads(zero_fill_missing=False)
         first = True
         bufs: List[Optional[torch.Tensor]] = [None] * len(self.params)
+        if delta is None or not self.defer_state:
+            self.settle_state()  # only the one-peer step below continues a pending step
         if momentum != 0:
-            if self.d_mom is None:
-                self.d_mom = torch.zeros_like(self.d_theta)
-                plain = self._make_views(self.d_mom)
+            if self._mom is None:
+                self._mom = torch.zeros_like(self._theta)
+                plain = self._make_views(self._mom)
                 self._views["mom_plain"] = plain
                 self._views["mom"] = [self._momentum_buffer(v) for v in plain]
                 self._ptrs["mom"] = [v.data_ptr() for v in plain]
@@ -1299,6 +1339,7 @@ class DeviceOuterMirror:
                     raise RuntimeError("momentum buffers exist for some outer parameters only")
                 first = not any(have)
                 if not first:
+                    self.settle_state()  # the caller's buffers replace the momentum arena's
                     copied = 0
                     with torch.no_grad():
                         for b, v, e in zip(host_bufs, self._views["mom_plain"],
@@ -1311,7 +1352,7 @@ class DeviceOuterMirror:
             else:
                 first = False  # the buffers this mirror returned last step
             self._mom_src = bufs
-        mom = self.d_mom if momentum != 0 else None
+        mom = self._mom if momentum != 0 else None
         sharded = delta is None and self._xmode in ("sharded", "a2a")
         q8 = delta is None and self._xmode == "q8"
         if (mom is not None and self._mom_stale and not first
@@ -1322,7 +1363,22 @@ class DeviceOuterMirror:
         # if they moved or were written since, sync_inner_model sees it and scatters again
         target, self._target = self._target, None
         write = target is not None
-        if delta is not None:  # one peer: the delta never leaves registers
+        if delta is not None and self.defer_state:
+            # one peer, θ and the momentum in arenas nobody reads but through d_theta / d_mom:
+            # they are stored every second step only. This step's stores are left out
+            # (dl_delta_pack_sgd_defer, 20 B/param instead of 28); the next one redoes it in
+            # registers from the wire it left, then steps (dl_delta_pack_sgd_resume, 32 B)
+            pend, self._pend = self._pend, None
+            if pend is None:
+                self.k.delta_pack_sgd_defer(self.tree, ALL, SLOT_INNER, self._theta, self.d_wire,
+                                            mom, lr, momentum, nesterov, first)
+                self._pend = (lr, momentum, nesterov, first)
+            else:
+                self.k.delta_pack_sgd_resume(self.tree, ALL, SLOT_INNER, self._theta,
+                                             self.d_wire, mom if pend[1] == 0 else self._mom,
+                                             pend, lr, momentum, nesterov, first)
+            self._mom_stale = False
+        elif delta is not None:  # one peer: the delta never leaves registers
             self.k.delta_pack_sgd(self.tree, ALL, SLOT_INNER, self.d_theta, self.d_wire, mom,
                                   lr, momentum, nesterov, first)
             self._mom_stale = False
@@ -1399,6 +1455,7 @@ class DeviceOuterMirror:
         its own collective, the pending /n left in the divisor."""
         if not self.adamw_ready():
             raise RuntimeError("adamw_step: the pending exchange is not the replicated one")
+        self.settle_state()
         tver = self._theta_version()
         delta = self._take_delta(tver) if self._delta is not None else None
         tver = self._relay_theta(tver)
@@ -1450,6 +1507,7 @@ class DeviceOuterMirror:
 
     def close(self) -> None:
         self._join()
+        self.settle_state()
         self.tree.close()
 
 
@@ -1630,7 +1688,14 @@ class LazyHostOuterMirror:
     opted-in sharded exchange at N > 1, reading `.grad` or the momentum is a collective over
     the DP group, as for the device placement (collective_read guards it). With an AdamW outer
     optimizer (optim.OuterAdamW, adamw_step) exp_avg and exp_avg_sq are two more host arenas,
-    kept coherent the same way."""
+    kept coherent the same way.
+
+    Because the twin's θ and momentum are read through these hooks alone, the one-peer SGD
+    step (fused, fp32 wire) stores them every second step only: a step that leaves them out
+    (dl_delta_pack_sgd_defer, 20 B/param) stays pending in the twin -- θ, the momentum and the
+    wire determine it bit for bit -- and the next step redoes it in registers before its own
+    (dl_delta_pack_sgd_resume, 32 B/param); whatever reads or writes θ or the momentum first
+    completes it (DeviceOuterMirror.settle_state). DILOCO_OUTER_DEFER_STATE=0 turns it off."""
 
     def __init__(self, outer_model: torch.nn.Module, device: torch.device, kernels=None,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = True,
@@ -1649,14 +1714,21 @@ class LazyHostOuterMirror:
                                      exchange)
         self._twin = twin
         self.fused, self.wire, self.exchange = fused, wire, exchange
+        from .utils import env_flag
+
+        # the one-peer SGD step stores θ and the momentum every second step only: the twin's
+        # arenas are read through this mirror's hooks alone, which complete a pending step
+        # first. DILOCO_OUTER_DEFER_STATE=0: every step stores them (one dl_delta_pack_sgd),
+        # as with a kernel set that has no defer / resume pair (the CPU oracle's of the tests)
+        self.dev.defer_state = (fused and wire == "f32"
+                                and env_flag("DILOCO_OUTER_DEFER_STATE", True)
+                                and hasattr(self.dev.k, "delta_pack_sgd_resume"))
         self.tree, self.offs, self.numels = self.dev.tree, self.dev.offs, self.dev.numels
         # host arenas, pageable by default: pinned and pageable measured the same for the step
         # (profiles/r04_placement_ab_order.txt) -- nothing crosses PCIe unless the host reads --
         # and pageable pages of the .grad / momentum arenas are not resident until a read
         # fills them (4 B/param resident per rank instead of 12 pinned).
         # DILOCO_HOST_PIN=1 pins them (one async DMA per read)
-        from .utils import env_flag
-
         self._pin = self.device.type == "cuda" and env_flag("DILOCO_HOST_PIN", False)
         self.h = {"theta": self._arena(zero=True), "grad": self._arena(), "mom": None,
                   "exp_avg": None, "exp_avg_sq": None}
@@ -1722,8 +1794,9 @@ class LazyHostOuterMirror:
                 self.dev.settle_grads()  # the pending delta / Σ / sharded gathers, then /n
             elif arena == "mom":
                 self.dev.gather_momentum()
-            src = {"theta": self.dev.d_theta, "grad": self.dev.d_wire, "mom": self.dev.d_mom,
-                   "exp_avg": self.dev.d_m1, "exp_avg_sq": self.dev.d_m2}[arena]
+            # d_theta / d_mom complete a pending step first; .grad needs none completed
+            src = getattr(self.dev, {"theta": "d_theta", "grad": "d_wire", "mom": "d_mom",
+                                     "exp_avg": "d_m1", "exp_avg_sq": "d_m2"}[arena])
             h = self.h[arena]
             h.copy_(src, non_blocking=self._pin)
             self._sync_stream()
@@ -1769,7 +1842,7 @@ class LazyHostOuterMirror:
                     if cur.data_ptr() != v.data_ptr():
                         v.copy_(cur)
                         _DATA.__set__(p, v)
-            if self._changed("theta", "outer parameters"):
+            if self._changed("theta", "outer parameters"):  # (d_theta: a pending step first)
                 dev.d_theta.copy_(self.h["theta"], non_blocking=self._pin)
                 self._ver["theta"] = self.h["theta"]._version
             if self.grads_touched:  # a .grad was assigned: values into the arena, or None
@@ -1789,6 +1862,7 @@ class LazyHostOuterMirror:
                         _GRAD.__set__(tp, dev._views["wire"][i])
                         dev.grads_touched = True
             if self._changed("grad", "outer gradients"):
+                dev.settle_state()  # a pending step meant the wire as it is now
                 dev.d_wire.copy_(self.h["grad"], non_blocking=self._pin)
                 self._ver["grad"] = self.h["grad"]._version
                 dev.grads_touched = True

@@ -169,6 +169,36 @@ DL_API int dl_delta_pack_sgd(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
                              float* mom_packed, float lr, float momentum, int32_t nesterov,
                              int32_t first_step, dl_stream_t stream);
 
+/* dl_delta_pack_sgd (fp32 wire) with the stores of θ and the momentum left out: the wire and
+ * inner[seg][j] receive what dl_delta_pack_sgd gives them, outer_packed and mom_packed keep the
+ * values they had. The step is then PENDING: (outer_packed, mom_packed, wire) and this call's
+ * hyper-parameters determine its θ and momentum bit for bit, and one of two calls completes it:
+ *   dl_unpack_sgd(wire, DL_F32, divisor 1, ..., the same lr / momentum / nesterov / first_step,
+ *                 inner_slot -1)            θ and the momentum stored, nothing else touched
+ *   dl_delta_pack_sgd_resume                the next outer step, below
+ * 20 B/param (16 on the first step) instead of 28: of the 16 B a step writes only the wire's 4
+ * are new information, and a written stream costs more than a read one. */
+DL_API int dl_delta_pack_sgd_defer(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
+                                   float* outer_packed, float* wire, float* mom_packed, float lr,
+                                   float momentum, int32_t nesterov, int32_t first_step,
+                                   dl_stream_t stream);
+
+/* The outer step after a pending one (dl_delta_pack_sgd_defer with the pending_* values):
+ *   θ, buf <- the pending step's, recomputed from outer_packed, mom_packed and wire[k]
+ *   g = θ - inner[seg][j]; wire[k] = g (in place: each element is read before it is written);
+ *   SGD as dl_unpack_sgd (divisor 1) with lr, momentum, nesterov, first_step;
+ *   outer_packed, mom_packed and inner[seg][j] stored
+ * Bit-identical to dl_delta_pack_sgd twice. The two sets of hyper-parameters are independent;
+ * mom_packed is needed when either momentum is not 0. 32 B/param (16 read, 16 written), so a
+ * defer / resume pair moves 52 B/param where two dl_delta_pack_sgd move 56, with 24 instead
+ * of 32 of them written. */
+DL_API int dl_delta_pack_sgd_resume(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
+                                    float* outer_packed, float* wire, float* mom_packed,
+                                    float pending_lr, float pending_momentum,
+                                    int32_t pending_nesterov, int32_t pending_first_step,
+                                    float lr, float momentum, int32_t nesterov,
+                                    int32_t first_step, dl_stream_t stream);
+
 /* a3+a4+a5 fused for an AdamW outer optimizer (src/utils.py:60-61, configs/optimizer/adamw.toml,
  * stepped at src/train.py:267): one element of torch's _single_tensor_adamw (amsgrad, maximize
  * and capturable off; beta1 > 0.5, where torch's lerp uses this formula), then sync_inner_model.

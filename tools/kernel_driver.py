@@ -35,6 +35,17 @@ def main():
     kept.step()
     for _ in range(reps):
         kept.step()
+    # the lazy host placement's pair: a step without the θ / momentum stores, then the step
+    # that redoes it in registers before its own (dl_delta_pack_sgd_defer / _resume)
+    from diloco_amd._lib import ALL_BUCKETS
+    from diloco_amd.plan import SLOT_INNER
+
+    hyper = (0.7, 0.9, True, False)
+    for _ in range(reps):
+        kept.k.delta_pack_sgd_defer(kept.tree, ALL_BUCKETS, SLOT_INNER, kept.theta, kept.wire,
+                                    kept.mom, *hyper)
+        kept.k.delta_pack_sgd_resume(kept.tree, ALL_BUCKETS, SLOT_INNER, kept.theta, kept.wire,
+                                     kept.mom, hyper, *hyper)
     # one bucket each, so every launch covers the whole tree: the int8 wire kernels and the
     # sharded step's dl_shard_sgd (one replica: the shard is the whole bucket)
     q8 = OuterSync(params, world_size=1, wire_dtype=torch.int8, bucket_cap_elems=0)

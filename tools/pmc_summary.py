@@ -19,12 +19,17 @@ from collections import defaultdict
 def short(name):
     # the outer-step body (csrc/dl_outer_step.h): OuterStep<gradient source, update rule> under
     # k_walk, or under k_flat for dl_shard_sgd; SgdRule's MODE 1 is the first step
+    m = re.search(r"FromDeltaAfterPending<[^<]*SgdRule<(\d)> >,[^<]*SgdRule<\d>", name)
+    if m:  # the step after a deferred one; the pending rule's MODE 1: that one was the first
+        return "delta_pack_sgd_resume" + ("_after_first" if m.group(1) == "1" else "")
     m = re.search(r"OuterStep<.*?\b(FromWire|FromDeltaKeptOnWire|FromDelta)\b.*?"
                   r"\b(AdamRule|SgdRule<(\d)>)", name)
     if m:
         src = {"FromWire": "unpack", "FromDelta": "delta", "FromDeltaKeptOnWire": "delta_pack"}
         v = "shard_sgd" if "k_flat" in name else src[m.group(1)] + (
             "_adamw" if m.group(2) == "AdamRule" else "_sgd")
+        if re.search(r"SgdRule<\d>, true>", name):  # kDefer: θ and the momentum not stored
+            v += "_defer"
         return v + ("_first" if m.group(3) == "1" else "")
     # most specific first: UnpackSgdQ8 before the plain bodies, DeltaPackPair before DeltaPack
     names = {"k_xgmi_reduce_sgd": "xgmi_reduce_sgd", "DeltaQ8": "delta_q8", "UnpackSgdQ8": "unpack_sgd_q8",
