@@ -707,6 +707,47 @@ DL_API int dl_shard_reduce_avg(const void* slices, int32_t wire_dtype, int32_t n
   return e == hipSuccess ? DL_OK : hip_fail(e, "dl_shard_reduce_avg");
 }
 
+DL_API int dl_shard_adamw(const void* wire, int32_t wire_dtype, int32_t divisor, float* outer,
+                          float* exp_avg, float* exp_avg_sq, int64_t n, float decay, float w1,
+                          float beta2, float w2, float neg_step_size, float bc2_sqrt, float eps,
+                          dl_stream_t s) {
+  if (n < 0) return fail(DL_E_ARG, "dl_shard_adamw: n %lld", (long long)n);
+  if (n == 0) return DL_OK;
+  DL_TRY(check_packed(wire, "dl_shard_adamw", "wire"));
+  DL_TRY(check_dtype(wire_dtype, "dl_shard_adamw"));
+  DL_TRY(check_packed(outer, "dl_shard_adamw", "outer"));
+  DL_TRY(check_packed(exp_avg, "dl_shard_adamw", "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, "dl_shard_adamw", "exp_avg_sq"));
+  if (divisor < 1) return fail(DL_E_ARG, "dl_shard_adamw: divisor %d", divisor);
+  if ((n + DL_CHUNK_ELEMS - 1) / DL_CHUNK_ELEMS > INT32_MAX)
+    return fail(DL_E_ARG, "dl_shard_adamw: shard too large");
+  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
+  hipError_t e = dl::launch_shard_adamw(wire, wire_dtype, divisor, outer, exp_avg, exp_avg_sq, n,
+                                        a, static_cast<hipStream_t>(s));
+  return e == hipSuccess ? DL_OK : hip_fail(e, "dl_shard_adamw");
+}
+
+DL_API int dl_shard_reduce_adamw(const void* slices, int32_t wire_dtype, int32_t n_slices,
+                                 int64_t len, float* outer, float* exp_avg, float* exp_avg_sq,
+                                 float* avg_out, float decay, float w1, float beta2, float w2,
+                                 float neg_step_size, float bc2_sqrt, float eps, dl_stream_t s) {
+  if (len < 0 || len % 4 != 0)
+    return fail(DL_E_ARG, "dl_shard_reduce_adamw: len %lld (a multiple of 4)", (long long)len);
+  if (n_slices < 1) return fail(DL_E_ARG, "dl_shard_reduce_adamw: n_slices %d", n_slices);
+  if (len == 0) return DL_OK;
+  DL_TRY(check_packed(slices, "dl_shard_reduce_adamw", "slices"));
+  DL_TRY(check_dtype(wire_dtype, "dl_shard_reduce_adamw"));
+  DL_TRY(check_packed(outer, "dl_shard_reduce_adamw", "outer"));
+  DL_TRY(check_packed(exp_avg, "dl_shard_reduce_adamw", "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, "dl_shard_reduce_adamw", "exp_avg_sq"));
+  if (avg_out && !dl::aligned16_host(avg_out))
+    return fail(DL_E_ALIGN, "dl_shard_reduce_adamw: avg_out not 16-B aligned");
+  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
+  hipError_t e = dl::launch_slices_adamw(slices, wire_dtype, n_slices, len, outer, exp_avg,
+                                         exp_avg_sq, avg_out, a, static_cast<hipStream_t>(s));
+  return e == hipSuccess ? DL_OK : hip_fail(e, "dl_shard_reduce_adamw");
+}
+
 DL_API int dl_ipc_handle(const void* ptr, void* handle, int64_t* offset) {
   if (!ptr || !handle || !offset) return fail(DL_E_ARG, "dl_ipc_handle: null argument");
   void* base = nullptr;

@@ -1,7 +1,7 @@
 // Device-side building blocks shared by the kernel translation units (dl_kernels.hip,
 // dl_q8.hip, dl_adamw.hip, dl_xgmi.hip): streaming memory ops, element conversions, the segment
 // walker and its launcher, and the element arithmetic of the two update rules (sgd1, adam1).
-// The outer-step body built from them is dl_outer_step.h.
+// The outer-step body built from them is dl_outer_step.h; its flat-shard forms are dl_flat.h.
 #pragma once
 #include <type_traits>
 

@@ -101,6 +101,13 @@ hipError_t launch_unpack_adamw(const Launch& L, const void* wire, int wire_dtype
                                float* outer, float* m1, float* m2, AdamArgs a, int inner_slot);
 hipError_t launch_delta_pack_adamw(const Launch& L, int inner_slot, float* outer, void* wire,
                                    int wire_dtype, float* m1, float* m2, AdamArgs a);
+// AdamW on a flat shard (after a reduce-scatter) and on the n slices an all_to_all left;
+// avg_out (fp32, may be null) receives the rank-order average
+hipError_t launch_shard_adamw(const void* wire, int wire_dtype, int divisor, float* outer,
+                              float* m1, float* m2, int64_t n, AdamArgs a, hipStream_t s);
+hipError_t launch_slices_adamw(const void* slices, int wire_dtype, int32_t n, int64_t len,
+                               float* outer, float* m1, float* m2, float* avg_out, AdamArgs a,
+                               hipStream_t s);
 hipError_t launch_gather(const Launch& L, int src_slot, void* packed, int dtype);
 hipError_t launch_scatter(const Launch& L, const float* packed, int dst_slot);
 hipError_t launch_serialize_f64(const double* src, int64_t numel, float m0, float m1, double* out,

@@ -11,7 +11,7 @@
 // The outer-step kernels are instantiations of the one body of dl_outer_step.h, gradient
 // source x update rule (the numerics, bit-exact against the reference: beside sgd1, dl_device.h):
 //   dl_unpack_sgd      FromWire x SgdRule             a3 /n + a4 + a5: reads wire, θ, buf
-//   dl_shard_sgd       the same body over a flat shard (k_flat below)
+//   dl_shard_sgd       the same body over a flat shard (k_flat, dl_flat.h)
 //   dl_delta_sgd       FromDelta x SgdRule            a2 + a4 + a5 at one peer: 24 B/param (20
 //                      on the first step) instead of 12 + 24 for dl_delta_pack + dl_unpack_sgd
 //   dl_delta_pack_sgd  FromDeltaKeptOnWire x SgdRule  dl_delta_sgd that also stores the packed
@@ -21,7 +21,7 @@
 //   dl_delta_pack_sgd_resume  FromDeltaAfterPending x SgdRule: the pending step redone in
 //                      registers, then dl_delta_pack_sgd: 32 B/param for two steps' state
 // (dl_adamw.hip: the same sources x AdamRule). The bodies in this file move data only.
-#include "dl_outer_step.h"
+#include "dl_flat.h"
 
 namespace dl {
 namespace {
@@ -524,28 +524,7 @@ hipError_t launch_unpack_sgd(const Launch& L, const void* wire, int wire_dtype, 
   });
 }
 
-// Sharded outer step: after the reduce-scatter each peer owns a contiguous 1/n of
-// every bucket; dl_unpack_sgd's body runs over it as flat 4096-element chunks (no tree, no
-// inner copy: θ is all-gathered and scattered to the inner params afterwards).
-template <class Body>
-__global__ void __launch_bounds__(kThreads) k_flat(int64_t n, Body body) {
-  for (int64_t base = int64_t(blockIdx.x) * DL_CHUNK_ELEMS; base < n;
-       base += int64_t(gridDim.x) * DL_CHUNK_ELEMS) {
-    Chunk ck;
-    ck.poff = base;
-    ck.len = int32_t(n - base < DL_CHUNK_ELEMS ? n - base : DL_CHUNK_ELEMS);
-    ck.seg = 0;
-    body.template run<true, kStNT>(ck, 0, nullptr, 0, int(threadIdx.x));  // NT loads + stores
-  }
-}
-
-template <class Body>
-static hipError_t run_flat(int64_t n, const Body& body, hipStream_t s) {
-  const int32_t grid = int32_t((n + DL_CHUNK_ELEMS - 1) / DL_CHUNK_ELEMS);
-  hipLaunchKernelGGL(k_flat<Body>, dim3(grid), dim3(kThreads), 0, s, n, body);
-  return hipGetLastError();
-}
-
+// dl_unpack_sgd's body over a flat shard (k_flat, dl_flat.h)
 hipError_t launch_shard_sgd(const void* wire, int wire_dtype, int divisor, float* outer, float* mom,
                             int64_t n, SgdArgs a, hipStream_t s) {
   return with_wire(wire, wire_dtype, divisor, [&](auto grad) {
@@ -575,45 +554,14 @@ __global__ void __launch_bounds__(kThreads)
   const int nn = N > 0 ? N : n;
   for (int64_t base = int64_t(blockIdx.x) * kSliceStep; base < len;
        base += int64_t(gridDim.x) * kSliceStep) {
-    const int32_t nv = int32_t((len - base) / 4 < kThreads * kSU ? (len - base) / 4 : kThreads * kSU);
+    const int32_t nv = slice_tile_rows(len, base, kSU);
     float* t0 = th + base;
     float* m0 = mom + base;
     float4 g[kSU], t[kSU], m[kSU];
-    if constexpr (N > 0) {
-      float4 w[N][kSU];
-#pragma unroll
-      for (int u = 0; u < kSU; ++u) {
-        const int v = u * kThreads + int(threadIdx.x);
-        if (v < nv) {
-#pragma unroll
-          for (int q = 0; q < N; ++q) w[q][u] = WireIO<W>::template ld4<true>(slices + q * len + base, v);
-          if (MODE != 3) t[u] = ldf4<true>(t0, v);
-          if (MODE == 2) m[u] = ldf4<true>(m0, v);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kSU; ++u) {
-        g[u] = w[0][u];
-#pragma unroll
-        for (int q = 1; q < N; ++q)
-          g[u] = make_float4(g[u].x + w[q][u].x, g[u].y + w[q][u].y, g[u].z + w[q][u].z,
-                             g[u].w + w[q][u].w);
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < kSU; ++u) {
-        const int v = u * kThreads + int(threadIdx.x);
-        if (v < nv) {
-          if (MODE != 3) t[u] = ldf4<true>(t0, v);
-          if (MODE == 2) m[u] = ldf4<true>(m0, v);
-          g[u] = WireIO<W>::template ld4<true>(slices + base, v);
-          for (int q = 1; q < nn; ++q) {
-            const float4 d = WireIO<W>::template ld4<true>(slices + q * len + base, v);
-            g[u] = make_float4(g[u].x + d.x, g[u].y + d.y, g[u].z + d.z, g[u].w + d.w);
-          }
-        }
-      }
-    }
+    slice_sum<N>(slices, nn, len, base, nv, g, [&](int u, int v) {
+      if (MODE != 3) t[u] = ldf4<true>(t0, v);
+      if (MODE == 2) m[u] = ldf4<true>(m0, v);
+    });
 #pragma unroll
     for (int u = 0; u < kSU; ++u) {
       const int v = u * kThreads + int(threadIdx.x);
@@ -634,9 +582,7 @@ __global__ void __launch_bounds__(kThreads)
 template <int N, typename W>
 static hipError_t slices_sgd_n(const W* w, int32_t n, int64_t len, float* th, float* mom,
                                SgdArgs a, hipStream_t s, bool avg_only) {
-  const int64_t step = kThreads * slice_rows<N>() * 4;
-  const int64_t blocks = (len + step - 1) / step;
-  const int32_t grid = int32_t(blocks < (1 << 20) ? blocks : (1 << 20));
+  const int32_t grid = slice_grid(len, slice_rows<N>());
   if (avg_only)
     hipLaunchKernelGGL((k_slices_sgd<N, W, 3>), dim3(grid), dim3(kThreads), 0, s, w, n, len, th, mom, a);
   else if (a.momentum == 0.f)

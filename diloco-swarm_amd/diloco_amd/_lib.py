@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get(
 )
 
 # constants mirrored from include/diloco_hip.h
-ABI_VERSION = 3
+ABI_VERSION = 4
 ALIGN_ELEMS = 64
 CHUNK_ELEMS = 4096
 ALL_BUCKETS = -1
@@ -91,6 +91,15 @@ SIGNATURES = {
         ctypes.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _f32, _f32, _i32, _i32, _vp],
     ),
     "dl_shard_reduce_avg": (ctypes.c_int, [_vp, _i32, _i32, _i64, _vp, _vp]),
+    "dl_shard_adamw": (
+        ctypes.c_int,
+        [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
+    ),
+    "dl_shard_reduce_adamw": (
+        ctypes.c_int,
+        [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
+         _vp],
+    ),
     "dl_delta_q8": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "dl_q8_reduce": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "dl_unpack_sgd_q8": (

@@ -31,7 +31,7 @@ def wire_code(dtype: torch.dtype) -> int:
 
 def adamw_scalars(lr: float, beta1: float, beta2: float, weight_decay: float, eps: float,
                   step: float) -> tuple:
-    """The seven per-step scalars of dl_unpack_adamw / dl_delta_pack_adamw (decay, w1, beta2,
+    """The seven per-step scalars of the dl_*_adamw entry points (decay, w1, beta2,
     w2, neg_step_size, bc2_sqrt, eps) in Python doubles, each expression written as torch's
     _single_tensor_adamw writes it; `step` is the count after this step. The C-ABI call narrows
     each to fp32 once, as torch does when the Python scalar meets the fp32 tensor."""
@@ -155,6 +155,22 @@ class HipKernels:
         """out = Σ of the n_slices equal slices in rank order / n (fp32 out, out's length)."""
         _lib.call("dl_shard_reduce_avg", slices.data_ptr(), wire_code(slices.dtype),
                   int(n_slices), out.numel(), out.data_ptr(), _s(out))
+
+    def shard_adamw(self, wire, divisor, theta, exp_avg, exp_avg_sq, scalars) -> None:
+        """Flat 1/n shard after a reduce-scatter: wire / divisor, then one AdamW step on theta,
+        exp_avg, exp_avg_sq (equal-length views); scalars from adamw_scalars."""
+        _lib.call("dl_shard_adamw", wire.data_ptr(), wire_code(wire.dtype), int(divisor),
+                  theta.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), theta.numel(),
+                  *scalars, _s(theta))
+
+    def shard_reduce_adamw(self, slices, n_slices, theta, exp_avg, exp_avg_sq, scalars,
+                           avg_out=None) -> None:
+        """Flat 1/n shard after an all_to_all: slices = n_slices equal slices (wire dtype) of
+        theta's length; Σ in rank order, /n (kept in avg_out, fp32, if given), then one AdamW
+        step on theta, exp_avg, exp_avg_sq (equal-length views)."""
+        _lib.call("dl_shard_reduce_adamw", slices.data_ptr(), wire_code(slices.dtype),
+                  int(n_slices), theta.numel(), theta.data_ptr(), exp_avg.data_ptr(),
+                  exp_avg_sq.data_ptr(), _ptr(avg_out), *scalars, _s(theta))
 
     def xgmi_reduce_sgd(self, wires, thetas, n, rank, lo, length, mom, lr, momentum, nesterov,
                         first, device=None) -> None:

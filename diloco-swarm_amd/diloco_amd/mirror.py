@@ -554,9 +554,13 @@ def _gather_momentum_of(args, kwargs) -> None:
         if isinstance(x, MomentumBuffer):
             r = x.__dict__.get("_dl_mirror")
             m = r() if r is not None else None
-            if m is not None and id(m) not in seen:
-                seen.add(id(m))
-                m.gather_momentum()
+            kind = x.__dict__.get("_dl_arena", "mom")
+            if m is not None and (id(m), kind) not in seen:
+                seen.add((id(m), kind))
+                if kind == "adam":
+                    m.gather_adam_state()
+                else:
+                    m.gather_momentum()
         elif isinstance(x, (list, tuple)):
             for y in x:
                 visit(y)
@@ -568,8 +572,9 @@ def _gather_momentum_of(args, kwargs) -> None:
 
 class MomentumBuffer(torch.Tensor):
     """`outer_optimizer.state[p]["momentum_buffer"]` of a fused device outer model (a view of
-    its packed momentum arena). Under the sharded exchange every rank's SGD pass updates only
-    its own 1/n of the momentum; the rest of the arena is gathered from the peers
+    its packed momentum arena), and likewise an OuterAdamW's exp_avg / exp_avg_sq (views of the
+    two Adam arenas, gathered together). Under the sharded exchange every rank's SGD pass updates
+    only its own 1/n of the momentum; the rest of the arena is gathered from the peers
     the first time anything reads the values -- any torch function on a buffer other than a
     metadata query, its pickling and its deep copy -- so every value a caller observes is the
     reference's full, replicated momentum (src/utils.py:62-63, torch SGD's state). That gather
@@ -633,8 +638,10 @@ class DeviceOuterMirror:
 
     An AdamW outer optimizer (optim.OuterAdamW) steps through adamw_step the same way: ONE
     dl_delta_pack_adamw at one peer (36 B/param), dl_unpack_adamw per bucket after the
-    replicated exchange at N > 1; exp_avg and exp_avg_sq are two more packed arenas whose
-    views are the optimizer's state."""
+    replicated exchange at N > 1, and under the sharded / a2a exchange dl_shard_adamw /
+    dl_shard_reduce_adamw on this rank's 1/n of every bucket, then the all_gather of θ
+    (_sharded_adamw); exp_avg and exp_avg_sq are two more packed arenas whose views are the
+    optimizer's state, sharded after such a step like the momentum and gathered on first read."""
 
     def __init__(self, outer_model: torch.nn.Module, device: torch.device, kernels=None,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = False,
@@ -735,8 +742,11 @@ class DeviceOuterMirror:
         self.d_m1: Optional[torch.Tensor] = None
         self.d_m2: Optional[torch.Tensor] = None
         self._adam_src = None
+        # after a sharded / a2a AdamW step both hold this rank's slices only, like the momentum
+        self._adam_stale = False
+        self._adam_shard = None  # (group, n, rank) of the steps that left them sharded
         # set by utils when an OuterAdamW is attached to the outer model and no exchange was
-        # asked for: its fused step needs the whole averaged wire on every rank (replicated)
+        # asked for: the exchange is then the replicated one (.grad and the AdamW state local)
         self.adamw_replicated = False
 
     # ---- the pending one-peer step -------------------------------------------------------
@@ -767,9 +777,12 @@ class DeviceOuterMirror:
         self.settle_state()
         self._mom = value
 
-    def _momentum_buffer(self, view: torch.Tensor) -> "MomentumBuffer":
+    def _momentum_buffer(self, view: torch.Tensor, arena: str = "mom") -> "MomentumBuffer":
+        """arena: what a read of the values gathers first, "mom" (gather_momentum) or "adam"
+        (gather_adam_state)."""
         t = view.as_subclass(MomentumBuffer)
         t.__dict__["_dl_mirror"] = weakref.ref(self)
+        t.__dict__["_dl_arena"] = arena
         return t
 
     def __deepcopy__(self, memo):  # a copied outer model starts without a mirror
@@ -943,6 +956,21 @@ class DeviceOuterMirror:
             a, e = self._own(b, n, r)
             dist.all_gather_into_tensor(self.d_mom[lo:hi], self.d_mom[a:e], group=g)
 
+    def gather_adam_state(self) -> None:
+        """exp_avg and exp_avg_sq whole again after sharded AdamW steps (each rank updated its
+        own slices): one agreed collective read, then an in-place all_gather per bucket for
+        each arena over the DP group of those steps."""
+        if not self._adam_stale:
+            return
+        g, n, r = self._adam_shard
+        collective_read(g, "exp_avg")
+        self._adam_stale = False
+        for arena in (self.d_m1, self.d_m2):
+            for b in range(self.tree.n_buckets):
+                lo, hi = self.tree.bucket_ranges[b]
+                a, e = self._own(b, n, r)
+                dist.all_gather_into_tensor(arena[lo:hi], arena[a:e], group=g)
+
     def _sharded_sgd(self, mom, lr, momentum, nesterov, first, target) -> None:
         """Per bucket: wait for its reduce_scatter (a2a: all_to_all, then dl_shard_reduce_avg
         into this rank's slice of the wire), dl_shard_sgd on this rank's slice of θ and the
@@ -981,6 +1009,49 @@ class DeviceOuterMirror:
         if mom is not None:
             self._mom_stale = True
             self._mom_shard = (g, n, r)
+
+    def _sharded_adamw(self, scalars, target) -> None:
+        """_sharded_sgd with the AdamW rule. Per bucket: wait for its reduce_scatter, then
+        dl_shard_adamw (/n) on this rank's slice of θ, exp_avg and exp_avg_sq -- after an
+        all_to_all ONE dl_shard_reduce_adamw instead (the rank-order sum, /n, the average kept
+        in this rank's slice of the wire, AdamW: one pass where SGD takes two) -- an in-place
+        RCCL all_gather of θ, and, one bucket behind, dl_scatter of the gathered θ into the
+        inner params."""
+        works, self._works = self._works, None
+        mode, n, r, g = self._xmode, self._xn, self._xrank, self._xgroup
+        write = target is not None
+        if write:
+            self.k.bind(self.tree, SLOT_INNER, target[0], self.device, key=tuple(target[1]))
+        nb = self.tree.n_buckets
+        ags = [None] * nb
+        for b in range(nb):
+            if works is not None:
+                works[b].wait()
+            lo, hi = self.tree.bucket_ranges[b]
+            a, e = self._own(b, n, r)
+            if mode == "a2a":
+                self.k.shard_reduce_adamw(self.d_recv[lo:hi], n, self.d_theta[a:e],
+                                          self.d_m1[a:e], self.d_m2[a:e], scalars,
+                                          avg_out=self.d_wire[a:e])
+            else:
+                self.k.shard_adamw(self.d_wire[a:e], self._div, self.d_theta[a:e],
+                                   self.d_m1[a:e], self.d_m2[a:e], scalars)
+            ags[b] = dist.all_gather_into_tensor(self.d_theta[lo:hi], self.d_theta[a:e],
+                                                 group=g, async_op=True)
+            if b >= 1:
+                ags[b - 1].wait()
+                if write:
+                    self.k.scatter(self.tree, b - 1, self.d_theta, SLOT_INNER)
+        ags[nb - 1].wait()
+        if write:
+            self.k.scatter(self.tree, nb - 1, self.d_theta, SLOT_INNER)
+        # the wire keeps this rank's slices (Σ; after an a2a reduce the average) for a later
+        # .grad read; both state arenas hold this rank's slices only
+        self._xmode = "sharded"
+        if mode == "a2a":
+            self._div = 1
+        self._adam_stale = True
+        self._adam_shard = (g, n, r)
 
     def _take_delta(self, tver_now=None) -> List[torch.Tensor]:
         """The pending delta's inner params, checked unchanged since compute_pseudo_gradient
@@ -1024,11 +1095,12 @@ class DeviceOuterMirror:
 
     def flush(self) -> None:
         """No host copy to write back (torch copies to the host on demand); completes the
-        deferred .grad work and gathers a sharded momentum (collectives under the sharded
-        exchange)."""
+        deferred .grad work and gathers a sharded momentum or AdamW state (collectives under
+        the sharded exchange)."""
         if self.fused:
             self.settle_grads()
             self.gather_momentum()
+            self.gather_adam_state()
 
     def _grad_views(self) -> None:
         if not self.fused or self.grads_touched:
@@ -1408,10 +1480,11 @@ class DeviceOuterMirror:
 
     # ---- the AdamW outer step (optim.OuterAdamW) -------------------------------------------
     def adamw_ready(self) -> bool:
-        """The fused AdamW pass covers what is pending: a recorded delta (one peer) or the
-        whole wire on this rank (replicated exchange, fp32 or bf16; eager mode). Not the
-        sharded / a2a slices nor the int8 slots: OuterAdamW then runs torch's own step."""
-        return self._delta is not None or self._xmode is None
+        """The fused AdamW pass covers what is pending: a recorded delta (one peer), the
+        whole wire on this rank (replicated exchange, fp32 or bf16; eager mode), or this rank's
+        slices after the sharded / a2a exchange. Not the int8 slots: OuterAdamW then runs
+        torch's own step."""
+        return self._delta is not None or self._xmode in (None, "sharded", "a2a")
 
     def _adam_state(self, host_m, host_v):
         """The packed exp_avg / exp_avg_sq arenas holding the optimizer's state: zeros when it
@@ -1422,7 +1495,7 @@ class DeviceOuterMirror:
             for name, arena in (("exp_avg", self.d_m1), ("exp_avg_sq", self.d_m2)):
                 plain = self._make_views(arena)
                 self._views[name + "_plain"] = plain
-                self._views[name] = [self._momentum_buffer(v) for v in plain]
+                self._views[name] = [self._momentum_buffer(v, "adam") for v in plain]
                 self._ptrs[name] = [v.data_ptr() for v in plain]
             fresh = True
         else:
@@ -1431,6 +1504,7 @@ class DeviceOuterMirror:
         ours = (src is not None and len(host_m) == len(src[0]) and len(host_v) == len(src[1])
                 and all(map(is_, host_m, src[0])) and all(map(is_, host_v, src[1])))
         if not ours:
+            whole = 0  # arenas written in whole from the caller's state (or zeroed)
             for name, host, arena in (("exp_avg", host_m, self.d_m1),
                                       ("exp_avg_sq", host_v, self.d_m2)):
                 have = [b is not None for b in host]
@@ -1440,10 +1514,16 @@ class DeviceOuterMirror:
                     if not any(have):
                         if not fresh:
                             arena.zero_()  # the optimizer's state was reset
+                        whole += 1
                         continue
+                    copied = 0
                     for b, v, e in zip(host, self._views[name + "_plain"], self._ptrs[name]):
                         if _DATA_PTR(b) != e or b.device != v.device:
                             v.copy_(b)  # e.g. a state_dict loaded into the optimizer
+                            copied += 1
+                    whole += copied == len(host)
+            if whole == 2:
+                self._adam_stale = False  # every slice of both arenas written from the caller's
         self._adam_src = (self._views["exp_avg"], self._views["exp_avg_sq"])
         return self._adam_src
 
@@ -1452,9 +1532,10 @@ class DeviceOuterMirror:
         kernels.adamw_scalars); returns the exp_avg and exp_avg_sq tensors (views of the packed
         arenas) for the optimizer state. One peer: dl_delta_pack_adamw (delta, .grad, AdamW, θ
         and the inner params); N > 1, replicated: dl_unpack_adamw per bucket, each waiting for
-        its own collective, the pending /n left in the divisor."""
+        its own collective, the pending /n left in the divisor; sharded / a2a: _sharded_adamw
+        on this rank's 1/n, after which exp_avg and exp_avg_sq hold this rank's slices."""
         if not self.adamw_ready():
-            raise RuntimeError("adamw_step: the pending exchange is not the replicated one")
+            raise RuntimeError("adamw_step: the pending exchange is the int8 one")
         self.settle_state()
         tver = self._theta_version()
         delta = self._take_delta(tver) if self._delta is not None else None
@@ -1462,11 +1543,17 @@ class DeviceOuterMirror:
         if delta is None:
             self._relay_grads(zero_fill_missing=False)
         bufs = self._adam_state(host_m, host_v)
+        sharded = delta is None and self._xmode in ("sharded", "a2a")
+        if self._adam_stale and not (
+                sharded and self._adam_shard == (self._xgroup, self._xn, self._xrank)):
+            self.gather_adam_state()  # a whole-tree pass needs every slice of the state
         target, self._target = self._target, None
         write = target is not None
         if delta is not None:  # one peer: the delta never leaves registers
             self.k.delta_pack_adamw(self.tree, ALL, SLOT_INNER, self.d_theta, self.d_wire,
                                     self.d_m1, self.d_m2, scalars)
+        elif sharded:  # N > 1, sharded / a2a exchange: this rank's 1/n, then all_gather(θ)
+            self._sharded_adamw(scalars, target)
         else:
             if write:
                 self.k.bind(self.tree, SLOT_INNER, target[0], self.device, key=tuple(target[1]))
@@ -1688,7 +1775,8 @@ class LazyHostOuterMirror:
     opted-in sharded exchange at N > 1, reading `.grad` or the momentum is a collective over
     the DP group, as for the device placement (collective_read guards it). With an AdamW outer
     optimizer (optim.OuterAdamW, adamw_step) exp_avg and exp_avg_sq are two more host arenas,
-    kept coherent the same way.
+    kept coherent the same way (after a sharded / a2a AdamW step the refresh gathers the twin's
+    two state arenas first: a collective, like the momentum's).
 
     Because the twin's θ and momentum are read through these hooks alone, the one-peer SGD
     step (fused, fp32 wire) stores them every second step only: a step that leaves them out
@@ -1794,6 +1882,8 @@ class LazyHostOuterMirror:
                 self.dev.settle_grads()  # the pending delta / Σ / sharded gathers, then /n
             elif arena == "mom":
                 self.dev.gather_momentum()
+            elif arena in _ADAM_ARENAS:
+                self.dev.gather_adam_state()  # both arenas whole before either is copied
             # d_theta / d_mom complete a pending step first; .grad needs none completed
             src = getattr(self.dev, {"theta": "d_theta", "grad": "d_wire", "mom": "d_mom",
                                      "exp_avg": "d_m1", "exp_avg_sq": "d_m2"}[arena])

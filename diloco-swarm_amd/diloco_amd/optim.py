@@ -10,7 +10,8 @@ outer model (mirror.DeviceOuterMirror) its state's momentum buffers are views of
 HBM momentum (mirror.MomentumBuffer).
 
 With cfg.type == "AdamW" (src/utils.py:60-61) and DILOCO_OUTER_ADAMW=fused it returns an
-`OuterAdamW`: torch.optim.AdamW's interface over dl_delta_pack_adamw / dl_unpack_adamw.
+`OuterAdamW`: torch.optim.AdamW's interface over dl_delta_pack_adamw / dl_unpack_adamw, and
+over dl_shard_adamw / dl_shard_reduce_adamw under the sharded and rank-order exchanges.
 """
 from __future__ import annotations
 
@@ -106,15 +107,20 @@ class OuterAdamW(AdamW):
     """The AdamW outer optimizer (src/utils.py:60-61, configs/optimizer/adamw.toml) with its
     step fused into the outer model's mirror: at one peer the whole outer step is one
     dl_delta_pack_adamw pass (36 B/param), at N > 1 one dl_unpack_adamw pass per bucket after
-    the replicated exchange. It IS a torch.optim.AdamW (param_groups, hooks, LR schedulers and
-    state_dict work unchanged; state[p]["step"] is torch's fp32 scalar tensor, exp_avg and
-    exp_avg_sq are views of the mirror's packed arenas), selected by get_optimizer under
-    DILOCO_OUTER_ADAMW=fused.
+    the replicated exchange; after the sharded exchange (asked for: exchange="sharded") one
+    dl_shard_adamw per bucket on this rank's 1/n, after the rank-order one
+    (DILOCO_DP_EXCHANGE=a2a, bit-exact at every replica count) one dl_shard_reduce_adamw, each
+    followed by the all_gather of θ. It IS a torch.optim.AdamW (param_groups, hooks, LR
+    schedulers and state_dict work unchanged; state[p]["step"] is torch's fp32 scalar tensor,
+    exp_avg and exp_avg_sq are views of the mirror's packed arenas), selected by get_optimizer
+    under DILOCO_OUTER_ADAMW=fused. After a sharded or rank-order step each rank holds its own
+    1/n of exp_avg and exp_avg_sq; reading either, or state_dict(), gathers the rest first -- a
+    collective over the DP group, like reading the momentum of a sharded OuterSGD.
 
     The fused pass is one element of torch's _single_tensor_adamw (include/diloco_hip.h).
     Whenever that contract or the mirror does not cover the step -- amsgrad, maximize,
     capturable, differentiable, beta1 <= 0.5, tensor hyper-parameters, more than one group,
-    parameters whose step counts differ, a sharded / a2a / int8 exchange, write_back "sync" or
+    parameters whose step counts differ, the int8 exchange, write_back "sync" or
     "deferred", no mirror at all (a CPU-only run) -- step() runs torch's own step body, exactly
     what a stock AdamW on this outer model does: never a silently different result."""
 

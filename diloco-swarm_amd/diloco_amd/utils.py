@@ -16,7 +16,10 @@ An AdamW outer optimizer (configs/optimizer/adamw.toml) is stock torch.optim.Ada
 DILOCO_OUTER_ADAMW=fused: then get_optimizer returns optim.OuterAdamW for an outer model, whose
 step is one dl_delta_pack_adamw pass at one peer (36 B/param) and one dl_unpack_adamw pass per
 bucket at N > 1; an outer model it is attached to takes the replicated exchange when none was
-asked for, and anything its kernels do not cover (see optim.OuterAdamW) runs torch's own step.
+asked for. Asked for, the sharded exchange steps this rank's 1/n with dl_shard_adamw and the
+rank-order one (DILOCO_DP_EXCHANGE=a2a) with dl_shard_reduce_adamw, exp_avg and exp_avg_sq
+staying sharded until read. Anything its kernels do not cover (the int8 wire; see
+optim.OuterAdamW) runs torch's own step.
 
 Placement of the outer model (`get_outer_model(..., placement=)`, default from the
 DILOCO_OUTER_PLACEMENT environment variable, "host" if unset):
@@ -111,8 +114,9 @@ def has_mirror(outer_model: nn.Module) -> bool:
 
 def _apply_adamw_mark(outer_model: nn.Module, m) -> None:
     """An outer model with an OuterAdamW attached and no exchange asked for takes the
-    replicated exchange (the device placement's implicit sharded default does not apply): the
-    fused AdamW pass needs the whole averaged wire, and .grad and the state stay local."""
+    replicated exchange (the device placement's implicit sharded default does not apply):
+    .grad, exp_avg and exp_avg_sq stay local on every rank, as torch's AdamW state is. The
+    sharded and rank-order steps (their state reads are collectives) are for who asks."""
     dev = getattr(m, "dev", m)  # the lazy host mirror's HBM twin
     if hasattr(dev, "adamw_replicated"):
         dev.adamw_replicated = bool(getattr(outer_model, _ADAMW, False)

@@ -30,7 +30,7 @@ extern "C" {
 
 #define DL_API __attribute__((visibility("default")))
 
-#define DL_ABI_VERSION 3
+#define DL_ABI_VERSION 4
 #define DL_ALIGN_ELEMS 64      /* segment start alignment in the packed space: 256 B of fp32 */
 #define DL_CHUNK_ELEMS 4096    /* work unit of every segment walker: 16 KiB of fp32 */
 #define DL_ALL_BUCKETS (-1)
@@ -276,6 +276,32 @@ DL_API int dl_shard_reduce_sgd(const void* slices, int32_t wire_dtype, int32_t n
  * ((s_0[k] + s_1[k]) + ... + s_{n-1}[k]) / n in fp32. len a multiple of 4; 16-B aligned. */
 DL_API int dl_shard_reduce_avg(const void* slices, int32_t wire_dtype, int32_t n_slices,
                                int64_t len, float* out, dl_stream_t stream);
+
+/* dl_shard_sgd with the AdamW rule: a3 /n + AdamW on one peer's shard after a reduce-scatter.
+ * Flat contiguous arrays of n elements, no tree and no inner write: g = wire[k] / divisor
+ * (divisor 1: untouched), then one element of dl_unpack_adamw on outer[k], exp_avg[k],
+ * exp_avg_sq[k], with its seven scalars in its order. The same body as dl_unpack_adamw over a
+ * flat shard, so bit-identical to it. The caller all-gathers `outer` and scatters it to the
+ * inner params (dl_scatter) afterwards; exp_avg and exp_avg_sq stay this peer's shards.
+ * 28 B per shard element (fp32 wire: 16 read, 12 written). All pointers non-null and 16-B
+ * aligned. */
+DL_API int dl_shard_adamw(const void* wire, int32_t wire_dtype, int32_t divisor, float* outer,
+                          float* exp_avg, float* exp_avg_sq, int64_t n, float decay, float w1,
+                          float beta2, float w2, float neg_step_size, float bc2_sqrt, float eps,
+                          dl_stream_t stream);
+
+/* dl_shard_reduce_sgd with the AdamW rule: a3 (Σ, /n) + AdamW on one peer's shard after an
+ * all_to_all. `slices` as for dl_shard_reduce_sgd; g = ((s_0 + s_1) + ... + s_{n-1}) / n in
+ * fp32 in rank order (n_slices 1: no division; a bf16 wire is summed in fp32 and never
+ * re-rounded), avg_out[k] = g when avg_out (fp32) is not NULL -- the average a later .grad
+ * read shows -- then one element of dl_unpack_adamw on outer[k], exp_avg[k], exp_avg_sq[k].
+ * len a multiple of 4; every pointer 16-B aligned, the two state pointers non-null. Reads
+ * n·sizeof(wire) + 12 B, writes 12 B (+ 4 with avg_out) per element. */
+DL_API int dl_shard_reduce_adamw(const void* slices, int32_t wire_dtype, int32_t n_slices,
+                                 int64_t len, float* outer, float* exp_avg, float* exp_avg_sq,
+                                 float* avg_out, float decay, float w1, float beta2, float w2,
+                                 float neg_step_size, float bc2_sqrt, float eps,
+                                 dl_stream_t stream);
 
 /* ---- int8 wire codec (not in the reference) --------------------------
  * One DL_Q8_SLOT_BYTES slot per chunk of the bucket, in chunk order: fp32 scale at byte 0,
