@@ -972,6 +972,76 @@ DL_API int dl_scatter(dl_tree_t t, int32_t b, const float* packed, int32_t dst_s
   return e == hipSuccess ? slot_end(t, dst_slot, L.stream, "dl_scatter") : hip_fail(e, "dl_scatter");
 }
 
+}  // extern "C"
+
+namespace {
+int check_partials(const double* p, const char* who) {
+  if (!p) return fail(DL_E_ARG, "%s: partials is null", who);
+  if (reinterpret_cast<uintptr_t>(p) & 7u)
+    return fail(DL_E_ALIGN, "%s: partials not 8-B aligned", who);
+  return DL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// Gradient-norm clipping (dl_norm.hip). The sum reads its slot once (NT loads, as dl_gather);
+// the two kernels that write gradients take dl_unpack_avg's launch and store policy.
+DL_API int dl_grad_sumsq(dl_tree_t t, int32_t b, int32_t src_slot, double* partials,
+                         dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_grad_sumsq", kAutoOther));
+  DL_TRY(check_slot(t, src_slot, "dl_grad_sumsq"));
+  DL_TRY(check_partials(partials, "dl_grad_sumsq"));
+  DL_TRY(slot_begin(t, src_slot, L.stream, "dl_grad_sumsq"));
+  hipError_t e = dl::launch_grad_sumsq(L, src_slot, partials);
+  return e == hipSuccess ? slot_end(t, src_slot, L.stream, "dl_grad_sumsq") : hip_fail(e, "dl_grad_sumsq");
+}
+
+DL_API int dl_unpack_avg_sumsq(dl_tree_t t, int32_t b, const void* wire, int32_t wire_dtype,
+                               int32_t divisor, int32_t dst_slot, float* dst_packed,
+                               double* partials, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_avg_sumsq", kAutoNT, Big::two_chunks));
+  DL_TRY(check_packed(wire, "dl_unpack_avg_sumsq", "wire"));
+  DL_TRY(check_dtype(wire_dtype, "dl_unpack_avg_sumsq"));
+  if (divisor < 1) return fail(DL_E_ARG, "dl_unpack_avg_sumsq: divisor %d", divisor);
+  if (dst_slot >= 0)
+    DL_TRY(check_slot(t, dst_slot, "dl_unpack_avg_sumsq"));
+  else
+    DL_TRY(check_packed(dst_packed, "dl_unpack_avg_sumsq", "dst_packed"));
+  DL_TRY(check_partials(partials, "dl_unpack_avg_sumsq"));
+  DL_TRY(slot_begin(t, dst_slot, L.stream, "dl_unpack_avg_sumsq"));
+  hipError_t e = dl::launch_unpack_avg_sumsq(L, wire, wire_dtype, divisor, dst_slot, dst_packed,
+                                             partials);
+  return e == hipSuccess ? slot_end(t, dst_slot, L.stream, "dl_unpack_avg_sumsq")
+                         : hip_fail(e, "dl_unpack_avg_sumsq");
+}
+
+DL_API int dl_norm_finish(const double* partials, int32_t n_partials, float max_norm, float* out2,
+                          dl_stream_t s) {
+  if (n_partials < 0) return fail(DL_E_ARG, "dl_norm_finish: n_partials %d", n_partials);
+  if (n_partials > 0) DL_TRY(check_partials(partials, "dl_norm_finish"));
+  if (!out2) return fail(DL_E_ARG, "dl_norm_finish: out2 is null");
+  if (reinterpret_cast<uintptr_t>(out2) & 3u)
+    return fail(DL_E_ALIGN, "dl_norm_finish: out2 not 4-B aligned");
+  hipError_t e = dl::launch_norm_finish(partials, n_partials, max_norm, out2,
+                                        static_cast<hipStream_t>(s));
+  return e == hipSuccess ? DL_OK : hip_fail(e, "dl_norm_finish");
+}
+
+DL_API int dl_scale_by(dl_tree_t t, int32_t b, int32_t slot, const float* coef, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_scale_by", kAutoNT, Big::two_chunks));
+  DL_TRY(check_slot(t, slot, "dl_scale_by"));
+  if (!coef) return fail(DL_E_ARG, "dl_scale_by: coef is null");
+  if (reinterpret_cast<uintptr_t>(coef) & 3u)
+    return fail(DL_E_ALIGN, "dl_scale_by: coef not 4-B aligned");
+  DL_TRY(slot_begin(t, slot, L.stream, "dl_scale_by"));
+  hipError_t e = dl::launch_scale_by(L, slot, coef);
+  return e == hipSuccess ? slot_end(t, slot, L.stream, "dl_scale_by") : hip_fail(e, "dl_scale_by");
+}
+
 DL_API int dl_serialize(const void* src, int32_t src_dtype, int64_t numel, float meta0,
                         float meta1, float* out, dl_stream_t s) {
   if (!src || !out) return fail(DL_E_ARG, "dl_serialize: null pointer");

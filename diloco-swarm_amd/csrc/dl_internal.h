@@ -108,6 +108,13 @@ hipError_t launch_shard_adamw(const void* wire, int wire_dtype, int divisor, flo
 hipError_t launch_slices_adamw(const void* slices, int wire_dtype, int32_t n, int64_t len,
                                float* outer, float* m1, float* m2, float* avg_out, AdamArgs a,
                                hipStream_t s);
+// gradient-norm clipping (dl_norm.hip): partials[c] = Σ g² of chunk c, c the tree's chunk index
+hipError_t launch_grad_sumsq(const Launch& L, int src_slot, double* partials);
+hipError_t launch_unpack_avg_sumsq(const Launch& L, const void* wire, int wire_dtype, int divisor,
+                                   int dst_slot, float* dst_packed, double* partials);
+hipError_t launch_norm_finish(const double* partials, int32_t n, float max_norm, float* out2,
+                              hipStream_t s);
+hipError_t launch_scale_by(const Launch& L, int slot, const float* coef);
 hipError_t launch_gather(const Launch& L, int src_slot, void* packed, int dtype);
 hipError_t launch_scatter(const Launch& L, const float* packed, int dst_slot);
 hipError_t launch_serialize_f64(const double* src, int64_t numel, float m0, float m1, double* out,

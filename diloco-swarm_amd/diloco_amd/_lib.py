@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get(
 )
 
 # constants mirrored from include/diloco_hip.h
-ABI_VERSION = 4
+ABI_VERSION = 5
 ALIGN_ELEMS = 64
 CHUNK_ELEMS = 4096
 ALL_BUCKETS = -1
@@ -55,6 +55,10 @@ SIGNATURES = {
     "dl_tuning_build": (ctypes.c_int, []),
     "dl_delta_pack": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp]),
     "dl_unpack_avg": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "dl_grad_sumsq": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "dl_unpack_avg_sumsq": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dl_norm_finish": (ctypes.c_int, [_vp, _i32, _f32, _vp, _vp]),
+    "dl_scale_by": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "dl_unpack_sgd": (
         ctypes.c_int,
         [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],

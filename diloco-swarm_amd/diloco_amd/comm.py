@@ -180,7 +180,20 @@ class DPSync:
                                               backend=dp_backend(), use_local_synchronization=True)
         return self._rccl_group
 
-    def sync_gradients(self, model: nn.Module) -> None:
+    def sync_gradients(self, model: nn.Module, max_norm: Optional[float] = None):
+        """max_norm: also clip the averaged gradients' 2-norm to it, as
+        clip_grad_norm_(model.parameters(), max_norm) right after the sync does
+        (src/train.py:251 then :255), and return the norm; None returns None. Device gradients
+        get both from one GradSync.sync(max_norm); every other branch syncs, then clips."""
+        norm = self._sync_gradients(model, max_norm)
+        if max_norm is None or norm is not None:
+            return norm
+        from .utils import clip_grad_norm_
+
+        return clip_grad_norm_(model.parameters(), max_norm)
+
+    def _sync_gradients(self, model: nn.Module, max_norm: Optional[float]):
+        """The sync; returns the norm where the sync clipped too (GradSync), else None."""
         num_peers = self.num_peers
         if num_peers == 1:
             return
@@ -216,19 +229,20 @@ class DPSync:
             gs = GradSync(params, self.dp_group(params[0].device), num_peers,
                           exchange=DP_EXCHANGE)
             self._grad_syncs[id(model)] = gs
-        gs.sync()
+        return gs.sync(max_norm)
 
 
 _DP: Dict[int, DPSync] = {}
 
 
-def dp_sync_gradients(world, model: nn.Module) -> None:
+def dp_sync_gradients(world, model: nn.Module, max_norm: Optional[float] = None):
     """Module-level entry for a reference TrainingComm whose sync_gradients delegates here
-    (INTEGRATION.md); one DPSync (and RCCL group) per World object."""
+    (INTEGRATION.md); one DPSync (and RCCL group) per World object. max_norm: see
+    DPSync.sync_gradients."""
     d = _DP.get(id(world))
     if d is None or d.world is not world:
         d = _DP[id(world)] = DPSync(world)
-    d.sync_gradients(model)
+    return d.sync_gradients(model, max_norm)
 
 
 class TrainingComm:
@@ -302,9 +316,10 @@ class TrainingComm:
         self.forward_recv_thread.load(tensor=None, metadata=metadata)
 
     # ---- the DP sync (outer-step hot path) ----------------------------------------------
-    def sync_gradients(self, model: nn.Module) -> None:
-        """src/comm.py:117-123 on RCCL + HIP (see DPSync)."""
-        self.dp.sync_gradients(model)
+    def sync_gradients(self, model: nn.Module, max_norm: Optional[float] = None):
+        """src/comm.py:117-123 on RCCL + HIP (see DPSync); max_norm: the clip of
+        src/train.py:255 with it, the norm returned."""
+        return self.dp.sync_gradients(model, max_norm)
 
     # ---- metrics aggregation (src/comm.py:125-149) ---------------------------------------
     def sync_outputs(self, outputs):

@@ -15,6 +15,12 @@ dl_shard_reduce_avg (Σ in rank order in fp32, / n, into this peer's shard) -> R
 of the averaged shards -> dl_unpack_avg (a copy): the same bus bytes as the all-reduce, an
 average that does not depend on RCCL's algorithm and is bit-exact against oracle/or_sum_avg at
 every n.
+
+sync(max_norm): the clip_grad_norm_ that follows the sync in the training loop
+(src/train.py:255), fused into it. Every dl_unpack_avg becomes dl_unpack_avg_sumsq, which holds
+each averaged gradient in registers on its way to .grad and leaves the chunk's Σ g²; after the
+last bucket dl_norm_finish and one dl_scale_by run on the same stream. Equal, bit for bit, to
+sync() followed by utils.clip_grad_norm_, without that call's read of every gradient.
 """
 from __future__ import annotations
 
@@ -68,25 +74,48 @@ class GradSync:
             self.a2a_avg = [torch.zeros(smax, **z) for _ in range(2)]
         # own stream, joined back into the caller's (see OuterSync.stream)
         self.stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
+        self.partials = None  # per-chunk Σ g² of sync(max_norm), created on first use
 
     def matches(self, params: Sequence[torch.Tensor]) -> bool:
         return len(params) == len(self.params) and all(
             a is b for a, b in zip(params, self.params))
 
-    def sync(self) -> None:
-        if self.stream is None:
-            self._sync()
-            return
-        cur = torch.cuda.current_stream(self.device)
-        if cur == self.stream:
-            self._sync()
-            return
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self._sync()
-        cur.wait_stream(self.stream)
+    def sync(self, max_norm: Optional[float] = None) -> Optional[torch.Tensor]:
+        """Average the gradients; with max_norm also clip them to it, as clip_grad_norm_ after
+        the sync would, and return the total norm (a 0-dim fp32 tensor on the device; no host
+        synchronisation). None: the sync alone, nothing returned."""
+        clip = None
+        if max_norm is not None:
+            if self.partials is None:
+                self.partials = torch.zeros(max(1, self.tree.n_chunks), dtype=torch.float64,
+                                            device=self.device)
+            # (norm, coefficient): a fresh pair per call, allocated on the caller's stream --
+            # the caller keeps the norm
+            clip = (float(max_norm), torch.empty(2, dtype=torch.float32, device=self.device))
+        cur = None if self.stream is None else torch.cuda.current_stream(self.device)
+        if cur is None or cur == self.stream:
+            self._sync(clip)
+        else:
+            self.stream.wait_stream(cur)
+            with torch.cuda.stream(self.stream):
+                self._sync(clip)
+            cur.wait_stream(self.stream)
+        return None if clip is None else clip[1][0]
 
-    def _sync(self) -> None:
+    def _unpack(self, b: int, divisor: int, clip) -> None:
+        if clip is None:
+            self.k.unpack_avg(self.tree, b, self.wire, divisor, SLOT_GRAD)
+        else:
+            self.k.unpack_avg_sumsq(self.tree, b, self.wire, divisor, SLOT_GRAD, self.partials)
+
+    def _sync(self, clip=None) -> None:
+        self._average(clip)
+        if clip is not None:  # every bucket's partial sums are in: the norm, then one scaling
+            max_norm, out2 = clip
+            self.k.norm_finish(self.partials, max_norm, out2)
+            self.k.scale_by(self.tree, _lib.ALL_BUCKETS, SLOT_GRAD, out2[1:])
+
+    def _average(self, clip) -> None:
         grads = [p.grad for p in self.params]
         for i, g in enumerate(grads):
             if g.dtype != torch.float32 or not g.is_contiguous():
@@ -102,17 +131,17 @@ class GradSync:
         # /1 still run, so the path is exercised on a one-GPU machine)
         local = self.local
         if self.a2a and not local:
-            self._sync_a2a()
+            self._sync_a2a(clip)
             return
         pipelined_buckets(
             self.tree.n_buckets,
             lambda b: self.k.gather(self.tree, b, SLOT_GRAD, self.wire),
             lambda b: _Done() if local else dist.all_reduce(
                 view(b), op=dist.ReduceOp.SUM, group=self.group, async_op=True),
-            lambda b: self.k.unpack_avg(self.tree, b, self.wire, self.world_size, SLOT_GRAD),
+            lambda b: self._unpack(b, self.world_size, clip),
         )
 
-    def _sync_a2a(self) -> None:
+    def _sync_a2a(self, clip=None) -> None:
         """gather(b) -> all_to_all(b) | rank-order average(b) -> all_gather(b) | copy back(b),
         overlapped across buckets like OuterSync's sharded step."""
         n, nb = self.world_size, self.tree.n_buckets
@@ -142,9 +171,9 @@ class GradSync:
                                                 group=self.group, async_op=True)
             if b >= 1:
                 ag[b - 1].wait()
-                self.k.unpack_avg(self.tree, b - 1, self.wire, 1, SLOT_GRAD)
+                self._unpack(b - 1, 1, clip)
         ag[nb - 1].wait()
-        self.k.unpack_avg(self.tree, nb - 1, self.wire, 1, SLOT_GRAD)
+        self._unpack(nb - 1, 1, clip)
 
     def close(self) -> None:
         self.tree.close()

@@ -214,6 +214,28 @@ class HipKernels:
         _lib.call("dl_unpack_avg", tree.handle, bucket, wire.data_ptr(), wire_code(wire.dtype),
                   int(divisor), int(dst_slot), _ptr(dst_packed), _s(wire))
 
+    # gradient-norm clipping (dl_norm.hip): partials = tree.n_chunks doubles, out2 = 2 floats
+    def grad_sumsq(self, tree, bucket, src_slot, partials) -> None:
+        """partials[c] = Σ g² over each chunk c of the bucket, in fp64."""
+        _lib.call("dl_grad_sumsq", tree.handle, bucket, int(src_slot), partials.data_ptr(),
+                  _s(partials))
+
+    def unpack_avg_sumsq(self, tree, bucket, wire, divisor, dst_slot, partials,
+                         dst_packed=None) -> None:
+        """unpack_avg that also leaves partials[c] of the values it stores."""
+        _lib.call("dl_unpack_avg_sumsq", tree.handle, bucket, wire.data_ptr(),
+                  wire_code(wire.dtype), int(divisor), int(dst_slot), _ptr(dst_packed),
+                  partials.data_ptr(), _s(wire))
+
+    def norm_finish(self, partials, max_norm, out2) -> None:
+        """out2[0] = the 2-norm from the partial sums, out2[1] = torch's clip coefficient."""
+        _lib.call("dl_norm_finish", partials.data_ptr(), partials.numel(), float(max_norm),
+                  out2.data_ptr(), _s(out2))
+
+    def scale_by(self, tree, bucket, slot, coef) -> None:
+        """slot *= coef[0] (a device scalar) in place; no memory touched when it is 1."""
+        _lib.call("dl_scale_by", tree.handle, bucket, int(slot), coef.data_ptr(), _s(coef))
+
     def gather(self, tree, bucket, src_slot, packed) -> None:
         _lib.call("dl_gather", tree.handle, bucket, src_slot, packed.data_ptr(),
                   wire_code(packed.dtype), _s(packed))

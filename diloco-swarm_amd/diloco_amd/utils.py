@@ -11,6 +11,8 @@ it raises. On the GPU:
   compute_pseudo_gradient(in, out)  out.grad = out - in   (dl_delta_pack)   src/utils.py:218-221
   sync_inner_model(out, in)         in = out              (dl_scatter)      src/utils.py:223-226
   get_optimizer(model, cfg)         AdamW | SGD (outer: OuterSGD, HIP)      src/utils.py:59-65
+  clip_grad_norm_(params, max_norm) torch's call at src/train.py:255 (dl_grad_sumsq ->
+                                    dl_norm_finish -> dl_scale_by)
 
 An AdamW outer optimizer (configs/optimizer/adamw.toml) is stock torch.optim.AdamW unless
 DILOCO_OUTER_ADAMW=fused: then get_optimizer returns optim.OuterAdamW for an outer model, whose
@@ -60,6 +62,7 @@ from __future__ import annotations
 
 import copy
 import os
+from collections import OrderedDict
 
 import torch
 import torch.nn as nn
@@ -69,7 +72,8 @@ from .kernels import default_kernels
 from .mirror import (DEFAULT_EXCHANGE, OUTER_EXCHANGES, OUTER_WIRES, WRITE_BACKS,
                      DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
 from .optim import OuterAdamW, OuterSGD
-from .plan import DEFAULT_BUCKET_CAP_ELEMS
+from ._lib import ALL_BUCKETS
+from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_GRAD
 
 _ATTR = "_diloco_mirror"
 _OUTER = "_diloco_outer"
@@ -314,6 +318,69 @@ def sync_inner_model(outer_model: nn.Module, inner_model: nn.Module) -> None:
     dev = _inner_device(inner_model)
     m = outer_mirror(outer_model, dev if dev.type != "cpu" else None)
     m.copy_to_inner(module_params(inner_model))
+
+
+# clip_grad_norm_'s trees: one per (backend, device, gradient sizes) seen; a training run has one
+# or two (a model, a pipeline stage). Bounded: the least recently used tree is closed.
+CLIP_CACHE_SIZE = 4
+_clip_cache: "OrderedDict[tuple, tuple]" = OrderedDict()
+
+
+def _clip_tree(k, device: torch.device, numels: tuple):
+    """(PackedTree over the gradients' sizes, its per-chunk partial sums), cached."""
+    key = (k.name, device, numels)
+    hit = _clip_cache.get(key)
+    if hit is not None:
+        _clip_cache.move_to_end(key)
+        return hit
+    tree = k.tree(numels, device)
+    partials = torch.zeros(max(1, tree.n_chunks), dtype=torch.float64, device=device)
+    _clip_cache[key] = (tree, partials)
+    while len(_clip_cache) > CLIP_CACHE_SIZE:
+        _, (old, _) = _clip_cache.popitem(last=False)
+        old.close()
+    return tree, partials
+
+
+def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0,
+                    error_if_nonfinite: bool = False, foreach=None) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ (src/train.py:255): same arguments, same return.
+
+    The 2-norm of fp32, contiguous gradients on one GPU runs as three HIP launches on the
+    current stream: dl_grad_sumsq (one read of every gradient, fp64 sums in a fixed order) ->
+    dl_norm_finish (norm and torch's fp32 clip coefficient, on the device) -> dl_scale_by
+    (g *= coef; touches no memory when nothing is clipped). No host synchronisation unless
+    error_if_nonfinite asks for the norm's value. Differences from torch: the norm is the
+    correctly rounded fp32 of an fp64 sum (within 2^-23 of torch's, relative), and it stays
+    finite where torch's fp32 accumulation overflows (|g| >~ 1.8e19). Anything else -- CPU
+    gradients, another norm_type, other dtypes, several devices -- is torch's own call."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    else:
+        parameters = list(parameters)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not (grads and float(norm_type) == 2.0 and device_path(grads[0]) and all(
+            g.dtype == torch.float32 and g.is_contiguous() and g.device == grads[0].device
+            and g.layout == torch.strided for g in grads)):
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type,
+                                              error_if_nonfinite, foreach)
+    k = default_kernels()
+    device = grads[0].device
+    with torch.no_grad():
+        tree, partials = _clip_tree(k, device, tuple(g.numel() for g in grads))
+        out2 = torch.empty(2, dtype=torch.float32, device=device)  # norm, coefficient
+        k.bind(tree, SLOT_GRAD, grads, device)  # .grad is reallocated every step
+        k.grad_sumsq(tree, ALL_BUCKETS, SLOT_GRAD, partials)
+        k.norm_finish(partials, float(max_norm), out2)
+        total_norm = out2[0]
+        if error_if_nonfinite and not bool(torch.isfinite(total_norm)):
+            raise RuntimeError(
+                f"The total norm of order {float(norm_type)} for gradients from "
+                "`parameters` is non-finite, so it cannot be clipped. To disable "
+                "this error and scale the gradients by the non-finite norm anyway, "
+                "set `error_if_nonfinite=False`")
+        k.scale_by(tree, ALL_BUCKETS, SLOT_GRAD, out2[1:])
+    return total_norm
 
 
 def get_optimizer(model: nn.Module, optimizer_config) -> Optimizer:

@@ -30,7 +30,7 @@ extern "C" {
 
 #define DL_API __attribute__((visibility("default")))
 
-#define DL_ABI_VERSION 4
+#define DL_ABI_VERSION 5
 #define DL_ALIGN_ELEMS 64      /* segment start alignment in the packed space: 256 B of fp32 */
 #define DL_CHUNK_ELEMS 4096    /* work unit of every segment walker: 16 KiB of fp32 */
 #define DL_ALL_BUCKETS (-1)
@@ -138,6 +138,38 @@ DL_API int dl_delta_pack(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
 DL_API int dl_unpack_avg(dl_tree_t tree, int32_t bucket, const void* wire, int32_t wire_dtype,
                          int32_t divisor, int32_t dst_slot, float* dst_packed,
                          dl_stream_t stream);
+
+/* ---- gradient-norm clipping ---------------------------------------------------------------
+ * torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm), norm_type 2, as the training
+ * loop calls it every step right after sync_gradients (src/train.py:255 after :251), on device
+ * gradients bound to a slot. `partials` is a device array of n_chunk doubles (dl_tree_query),
+ * indexed by the tree's chunk index; a bucket launch writes exactly its chunk range
+ * (dl_tree_bucket_chunks). All sums are fp64 in a fixed order (dl_norm.hip; restated in
+ * tests/clip_restatement.py), so the norm is a function of the values and the tensor sizes
+ * only: not of addresses, the grid (dl_tree_tune) or the bucket split. Unlike torch's fp32
+ * accumulation it does not overflow at |g| >~ 1.8e19.
+ *
+ * dl_grad_sumsq: partials[c] = Σ g² over chunk c of slot src_slot. One read, 4 B/param. */
+DL_API int dl_grad_sumsq(dl_tree_t tree, int32_t bucket, int32_t src_slot, double* partials,
+                         dl_stream_t stream);
+/* dl_unpack_avg that also writes partials[c] = Σ over the fp32 values it stores (after the
+ * division). The destination bytes are dl_unpack_avg's, the partials dl_grad_sumsq's on that
+ * destination: the norm of the averaged gradients costs no pass of its own. 8 B/param. */
+DL_API int dl_unpack_avg_sumsq(dl_tree_t tree, int32_t bucket, const void* wire,
+                               int32_t wire_dtype, int32_t divisor, int32_t dst_slot,
+                               float* dst_packed, double* partials, dl_stream_t stream);
+/* One workgroup: out2[0] = norm = float(sqrt(Σ partials[0:n_partials))), out2[1] = the clip
+ * coefficient in torch's fp32 operations: c = (1 / (norm + 1e-6f)) * max_norm (torch evaluates
+ * `max_norm / tensor` as reciprocal then multiply), coef = c < 1 ? c : (c is NaN ? c : 1).
+ * n_partials 0: norm 0. out2: two floats of device memory. */
+DL_API int dl_norm_finish(const double* partials, int32_t n_partials, float max_norm,
+                          float* out2, dl_stream_t stream);
+/* g[seg][j] *= *coef in place on slot `slot`, coef read from device memory by the kernel (no
+ * host synchronisation). *coef == 1.0f: the kernel touches no gradient memory at all, which
+ * equals torch's multiplication by 1.0 bit for bit; a NaN or zero coefficient multiplies.
+ * 8 B/param when it clips, none when it does not. */
+DL_API int dl_scale_by(dl_tree_t tree, int32_t bucket, int32_t slot, const float* coef,
+                       dl_stream_t stream);
 
 /* a3+a4+a5 fused: unpack the summed wire, average, outer SGD (torch.optim.SGD
  * _single_tensor_sgd as built by src/utils.py:62-63 and stepped at src/train.py:267),
