@@ -1042,6 +1042,29 @@ DL_API int dl_scale_by(dl_tree_t t, int32_t b, int32_t slot, const float* coef, 
   return e == hipSuccess ? slot_end(t, slot, L.stream, "dl_scale_by") : hip_fail(e, "dl_scale_by");
 }
 
+// The inner AdamW step (dl_inner.hip): dl_unpack_adamw's launch, load and store policy. Whether
+// NT stores suit θ, which the next forward pass re-reads, is not measured.
+DL_API int dl_adamw_step(dl_tree_t t, int32_t b, int32_t param_slot, int32_t grad_slot,
+                         float* exp_avg, float* exp_avg_sq, const float* coef, float decay,
+                         float w1, float beta2, float w2, float neg_step_size, float bc2_sqrt,
+                         float eps, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_adamw_step", kAutoUnpackSgd));
+  DL_TRY(check_slot(t, param_slot, "dl_adamw_step"));
+  DL_TRY(check_slot(t, grad_slot, "dl_adamw_step"));
+  DL_TRY(check_packed(exp_avg, "dl_adamw_step", "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, "dl_adamw_step", "exp_avg_sq"));
+  if (reinterpret_cast<uintptr_t>(coef) & 3u)
+    return fail(DL_E_ALIGN, "dl_adamw_step: coef not 4-B aligned");
+  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
+  DL_TRY(slot_begin(t, param_slot, L.stream, "dl_adamw_step"));
+  DL_TRY(slot_begin(t, grad_slot, L.stream, "dl_adamw_step"));
+  hipError_t e = dl::launch_adamw_step(L, param_slot, grad_slot, exp_avg, exp_avg_sq, coef, a);
+  if (e != hipSuccess) return hip_fail(e, "dl_adamw_step");
+  DL_TRY(slot_end(t, param_slot, L.stream, "dl_adamw_step"));
+  return slot_end(t, grad_slot, L.stream, "dl_adamw_step");
+}
+
 DL_API int dl_serialize(const void* src, int32_t src_dtype, int64_t numel, float meta0,
                         float meta1, float* out, dl_stream_t s) {
   if (!src || !out) return fail(DL_E_ARG, "dl_serialize: null pointer");

@@ -115,6 +115,10 @@ hipError_t launch_unpack_avg_sumsq(const Launch& L, const void* wire, int wire_d
 hipError_t launch_norm_finish(const double* partials, int32_t n, float max_norm, float* out2,
                               hipStream_t s);
 hipError_t launch_scale_by(const Launch& L, int slot, const float* coef);
+// the inner AdamW step (dl_inner.hip): θ in place in param_slot, g read from grad_slot (times
+// *coef when coef is not null), m1 / m2 packed
+hipError_t launch_adamw_step(const Launch& L, int param_slot, int grad_slot, float* m1, float* m2,
+                             const float* coef, AdamArgs a);
 hipError_t launch_gather(const Launch& L, int src_slot, void* packed, int dtype);
 hipError_t launch_scatter(const Launch& L, const float* packed, int dst_slot);
 hipError_t launch_serialize_f64(const double* src, int64_t numel, float m0, float m1, double* out,

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get(
 )
 
 # constants mirrored from include/diloco_hip.h
-ABI_VERSION = 5
+ABI_VERSION = 6
 ALIGN_ELEMS = 64
 CHUNK_ELEMS = 4096
 ALL_BUCKETS = -1
@@ -83,6 +83,10 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
          _vp],
+    ),
+    "dl_adamw_step": (
+        ctypes.c_int,
+        [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
     ),
     "dl_pack_sgd_tiled": (
         ctypes.c_int,

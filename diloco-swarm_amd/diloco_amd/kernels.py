@@ -129,6 +129,15 @@ class HipKernels:
                   wire.data_ptr(), wire_code(wire.dtype), exp_avg.data_ptr(),
                   exp_avg_sq.data_ptr(), *scalars, _s(theta))
 
+    def adamw_step(self, tree, bucket, param_slot, grad_slot, exp_avg, exp_avg_sq, scalars,
+                   coef=None) -> None:
+        """The inner AdamW step, one pass on the current stream: θ in place in the bound
+        param_slot, g read from the bound grad_slot (times coef[0], a device scalar, when
+        given: the gradients stay unscaled), exp_avg / exp_avg_sq packed arenas in the tree's
+        layout; scalars from adamw_scalars."""
+        _lib.call("dl_adamw_step", tree.handle, bucket, int(param_slot), int(grad_slot),
+                  exp_avg.data_ptr(), exp_avg_sq.data_ptr(), _ptr(coef), *scalars, _s(exp_avg))
+
     def pack_sgd_tiled(self, tree, bucket, inner_slot, theta, wire, mom, lr, momentum,
                        nesterov, first, tile_chunks) -> None:
         """One peer: delta_pack then unpack_sgd (divisor 1) tile by tile (Infinity-Cache

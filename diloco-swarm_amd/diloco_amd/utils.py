@@ -23,6 +23,11 @@ rank-order one (DILOCO_DP_EXCHANGE=a2a) with dl_shard_reduce_adamw, exp_avg and 
 staying sharded until read. Anything its kernels do not cover (the int8 wire; see
 optim.OuterAdamW) runs torch's own step.
 
+The inner optimizer (AdamW on a model that is not an outer model) is stock torch.optim.AdamW
+unless DILOCO_INNER_ADAMW=fused: then get_optimizer returns optim.InnerAdamW, whose step is one
+dl_adamw_step pass over the model's own tensors (28 B/param) after the clip above, or with the
+clip folded in through InnerAdamW.clip_grad_norm_.
+
 Placement of the outer model (`get_outer_model(..., placement=)`, default from the
 DILOCO_OUTER_PLACEMENT environment variable, "host" if unset):
 
@@ -71,7 +76,7 @@ from torch.optim import SGD, AdamW, Optimizer
 from .kernels import default_kernels
 from .mirror import (DEFAULT_EXCHANGE, OUTER_EXCHANGES, OUTER_WIRES, WRITE_BACKS,
                      DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
-from .optim import OuterAdamW, OuterSGD
+from .optim import InnerAdamW, OuterAdamW, OuterSGD
 from ._lib import ALL_BUCKETS
 from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_GRAD
 
@@ -85,6 +90,7 @@ _EXCHANGE = "_diloco_exchange"
 _EXCHANGE_ASKED = "_diloco_exchange_asked"  # by argument or DILOCO_OUTER_EXCHANGE
 _ADAMW = "_diloco_adamw"  # an optim.OuterAdamW is attached
 OUTER_ADAMW = ("torch", "fused")
+INNER_ADAMW = ("torch", "fused")  # DILOCO_INNER_ADAMW: the inner optimizer's step
 _PENDING = "_diloco_pending_device"  # placement="device" built before the inner model moved
 PLACEMENTS = ("host", "device")
 _TRUE = ("1", "true", "on", "yes")
@@ -385,13 +391,22 @@ def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0,
 
 def get_optimizer(model: nn.Module, optimizer_config) -> Optimizer:
     """src/utils.py:59-65. SGD on the outer model (from get_outer_model) -> OuterSGD; AdamW on
-    it under DILOCO_OUTER_ADAMW=fused -> OuterAdamW (unset or "torch": stock AdamW)."""
+    it under DILOCO_OUTER_ADAMW=fused -> OuterAdamW (unset or "torch": stock AdamW). AdamW on
+    any other model (the inner optimizer, src/train.py:418) under DILOCO_INNER_ADAMW=fused ->
+    InnerAdamW (unset or "torch": stock AdamW)."""
     if optimizer_config.type == "AdamW":
         knob = (os.environ.get("DILOCO_OUTER_ADAMW") or "torch").strip().lower()
         if knob not in OUTER_ADAMW:
             raise ValueError(f"DILOCO_OUTER_ADAMW={knob!r}: one of {OUTER_ADAMW}")
+        inner_knob = (os.environ.get("DILOCO_INNER_ADAMW") or "torch").strip().lower()
+        if inner_knob not in INNER_ADAMW:
+            raise ValueError(f"DILOCO_INNER_ADAMW={inner_knob!r}: one of {INNER_ADAMW}")
         if knob == "fused" and getattr(model, _OUTER, False):
             return OuterAdamW(model, lr=optimizer_config.lr,
+                              weight_decay=optimizer_config.weight_decay,
+                              betas=optimizer_config.betas)
+        if inner_knob == "fused" and not getattr(model, _OUTER, False):
+            return InnerAdamW(model.parameters(), lr=optimizer_config.lr,
                               weight_decay=optimizer_config.weight_decay,
                               betas=optimizer_config.betas)
         return AdamW(model.parameters(), lr=optimizer_config.lr,

@@ -30,7 +30,7 @@ extern "C" {
 
 #define DL_API __attribute__((visibility("default")))
 
-#define DL_ABI_VERSION 5
+#define DL_ABI_VERSION 6
 #define DL_ALIGN_ELEMS 64      /* segment start alignment in the packed space: 256 B of fp32 */
 #define DL_CHUNK_ELEMS 4096    /* work unit of every segment walker: 16 KiB of fp32 */
 #define DL_ALL_BUCKETS (-1)
@@ -260,6 +260,26 @@ DL_API int dl_delta_pack_adamw(dl_tree_t tree, int32_t bucket, int32_t inner_slo
                                float* exp_avg_packed, float* exp_avg_sq_packed, float decay,
                                float w1, float beta2, float w2, float neg_step_size,
                                float bc2_sqrt, float eps, dl_stream_t stream);
+
+/* The INNER optimizer's AdamW step (src/train.py:257, every training step, right after
+ * clip_grad_norm_ at :255) on the inner model's own tensors, one pass:
+ *   g' = coef ? g[seg][j] * *coef : g[seg][j]   (a separate, rounded fp32 multiply)
+ *   one element of dl_unpack_adamw's arithmetic on θ = param[seg][j], m = exp_avg[k],
+ *   v = exp_avg_sq[k] with g', its seven scalars in its order:
+ *     θ = θ*decay;  m = fma(w1, g' - m, m);  v = v*beta2;  v = fma(w2*g', g', v)
+ *     den = sqrt(v)/bc2_sqrt + eps;  θ = θ + (neg_step_size*m)/den
+ * θ is read and written in place through param_slot (per-tensor storage), g is only read
+ * through grad_slot; both slots must be bound. exp_avg and exp_avg_sq are packed fp32 arenas in
+ * the tree's layout (16-B aligned; zeros are the first step; their padding is never written).
+ * coef is a device pointer (dl_norm_finish's out2 + 1: the pending clip coefficient) or NULL;
+ * the kernel reads it, so no host synchronisation. There is no special case for *coef == 1:
+ * multiplying by 1 is the identity. coef = c equals dl_scale_by(c) followed by coef = NULL bit
+ * for bit, without the gradients being written. Results do not depend on the tensors'
+ * alignment, the grid or the bucket split. 28 B/param: g, θ, m, v read, θ, m, v written. */
+DL_API int dl_adamw_step(dl_tree_t tree, int32_t bucket, int32_t param_slot, int32_t grad_slot,
+                         float* exp_avg_packed, float* exp_avg_sq_packed, const float* coef,
+                         float decay, float w1, float beta2, float w2, float neg_step_size,
+                         float bc2_sqrt, float eps, dl_stream_t stream);
 
 /* a2 -> a3 -> a4 -> a5 at ONE peer as the two-kernel pipeline (dl_delta_pack then
  * dl_unpack_sgd with divisor 1; src/utils.py:221, src/comm.py:118-119, src/train.py:267,
