@@ -391,7 +391,8 @@ constexpr int32_t kAutoDeltaQ8 = DL_TUNE_NT_LOADS | DL_TUNE_NT_STORES;
 constexpr int32_t kBigLaunchChunks = (1 << 28) / DL_CHUNK_ELEMS;
 constexpr int32_t kAutoUnpackSgd = DL_TUNE_NT_LOADS | DL_TUNE_NT_STORES;
 // Kernels whose output no kernel re-reads next (dl_scatter: the inner params; dl_unpack_avg:
-// gradients; dl_unpack_sgd_q8: θ, momentum, inner) store non-temporally at every size. Round 2
+// gradients; dl_unpack_sgd_q8: θ, momentum, inner; dl_unpack_adamw_q8: θ, exp_avg, exp_avg_sq,
+// inner) store non-temporally at every size. Round 2
 // chose plain stores below 2^28 elements for the first two and write-through (sc1) for the int8
 // unpack from a cold timing whose end event did not wait for the lines a launch leaves dirty in
 // the Infinity Cache. Charged with that write-back (tools/cold_sweep.py --flushed,
@@ -946,6 +947,27 @@ DL_API int dl_unpack_sgd_q8(dl_tree_t t, int32_t b, const void* slots, float* ou
                                           inner_slot);
   return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_sgd_q8")
                          : hip_fail(e, "dl_unpack_sgd_q8");
+}
+
+// dl_unpack_sgd_q8's launch and policy with the AdamW rule: θ, exp_avg, exp_avg_sq and inner are
+// not re-read by a kernel next
+DL_API int dl_unpack_adamw_q8(dl_tree_t t, int32_t b, const void* slots, float* outer,
+                              float* exp_avg, float* exp_avg_sq, float decay, float w1,
+                              float beta2, float w2, float neg_step_size, float bc2_sqrt,
+                              float eps, int32_t inner_slot, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_adamw_q8", kAutoNT));
+  DL_TRY(check_packed(slots, "dl_unpack_adamw_q8", "slots"));
+  DL_TRY(check_packed(outer, "dl_unpack_adamw_q8", "outer"));
+  DL_TRY(check_packed(exp_avg, "dl_unpack_adamw_q8", "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, "dl_unpack_adamw_q8", "exp_avg_sq"));
+  DL_TRY(check_slot(t, inner_slot, "dl_unpack_adamw_q8", true));
+  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_adamw_q8"));
+  hipError_t e = dl::launch_unpack_adamw_q8(L, static_cast<const uint8_t*>(slots), outer, exp_avg,
+                                            exp_avg_sq, a, inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_adamw_q8")
+                         : hip_fail(e, "dl_unpack_adamw_q8");
 }
 
 DL_API int dl_gather(dl_tree_t t, int32_t b, int32_t src_slot, void* packed, int32_t dtype,

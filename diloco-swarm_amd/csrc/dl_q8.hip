@@ -10,9 +10,11 @@
 //   dl_q8_reduce      avg = (Σ_r q_r·s_r) / n in rank order; re-quantised with its own amax
 //   all_gather        every peer receives every averaged slot (identical on all peers)
 //   dl_unpack_sgd_q8  g = q·s; SGD exactly as dl_unpack_sgd; inner = θ
+//   dl_unpack_adamw_q8  the same slots under the AdamW rule: g = q·s; adam1 on θ, exp_avg and
+//                     exp_avg_sq exactly as dl_unpack_adamw (divisor 1); inner = θ
 // Quantiser: s = amax / 127 (IEEE division); q = s == 0 ? 0 : clamp(rint(x / s), -127, 127);
 // dequantised value q·s. Bus bytes per peer 2(n-1)/n · 1.016 B/param vs 8(n-1)/n for fp32.
-#include "dl_device.h"
+#include "dl_outer_step.h"
 
 namespace dl {
 namespace {
@@ -214,6 +216,97 @@ struct UnpackSgdQ8 {
   }
 };
 
+// UnpackSgdQ8's slot side (one 16-B payload load per lane, the LDS round trip, the wave-uniform
+// scale) under the AdamW rule, laid out as the AdamW body of dl_outer_step.h: the payload and
+// every 16-B load of θ, exp_avg and exp_avg_sq are issued before the LDS round trip, the rule
+// (AdamRule: adam1, written once) runs per component on the rows inside the chunk only, and
+// the stores leave one stream at a time: θ, exp_avg, exp_avg_sq, inner. Reads 1.016 + 12 B,
+// writes 12 B (+ 4 with the inner write) per param.
+struct UnpackAdamWQ8 {
+  static constexpr int K = AdamRule::kStates;
+  const uint8_t* slots;
+  int c0;
+  float* outer;
+  AdamRule rule;
+  int inner_slot;
+
+  template <int J>
+  __device__ __forceinline__ void step(float g, float4 (&m)[K][kUnroll], int u, float4& t) const {
+    float e[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) e[k] = comp<J>(m[k][u]);
+    rule.apply(g, e, comp<J>(t));
+#pragma unroll
+    for (int k = 0; k < K; ++k) comp<J>(m[k][u]) = e[k];
+  }
+
+  template <bool NTL, int NTS>
+  __device__ __forceinline__ void run(const Chunk& ck, int c, void* const* caddr, int nchunk, int tid) const {
+    float* in = inner_slot >= 0 ? slot_ptr<float>(caddr, nchunk, inner_slot, c) : nullptr;
+    const uint8_t* slot = slots + size_t(c - c0) * DL_Q8_SLOT_BYTES;
+    const uint8_t* q = slot + kQ8Header;
+    const float s = *reinterpret_cast<const float*>(slot);
+    float* th = outer + ck.poff;
+    float* sp[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) sp[k] = rule.state(k) + ck.poff;
+    auto one = [&](int i) {
+      const float g = float(int8_t(q[i])) * s;
+      float t1 = th[i];
+      float e[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) e[k] = sp[k][i];
+      rule.apply(g, e, t1);
+      th[i] = t1;
+#pragma unroll
+      for (int k = 0; k < K; ++k) sp[k][i] = e[k];
+      if (in) in[i] = t1;
+    };
+    if (in == nullptr || aligned16(in)) {
+      const int nv = ck.len >> 2;
+      uint32_t w[kUnroll];
+      float4 t[kUnroll], m[K][kUnroll];
+      __shared__ u32x4 stage[DL_CHUNK_ELEMS / 16];
+      // the whole slot payload (zero past the chunk's length), as in UnpackSgdQ8
+      const u32x4 qv = __builtin_nontemporal_load((const DL_GLOBAL u32x4*)q + tid);
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const int v = u * kThreads + tid;
+        if (v < nv) {
+          t[u] = ldf4<NTL>(th, v);
+#pragma unroll
+          for (int k = 0; k < K; ++k) m[k][u] = ldf4<NTL>(sp[k], v);
+        }
+      }
+      stage[tid] = qv;
+      __syncthreads();
+      const uint32_t* st32 = reinterpret_cast<const uint32_t*>(stage);
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) w[u] = st32[u * kThreads + tid];
+      __syncthreads();  // `stage` is reused by the workgroup's next chunk
+      static_assert(AdamRule::kSkipPastChunk, "rows past the chunk do no arithmetic");
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        if (u * kThreads + tid < nv) {
+          const float4 g = unpack4(w[u], s);
+          step<0>(g.x, m, u, t[u]);
+          step<1>(g.y, m, u, t[u]);
+          step<2>(g.z, m, u, t[u]);
+          step<3>(g.w, m, u, t[u]);
+        }
+      }
+      store_rows<NTS>(th, t, nv, tid);
+#pragma unroll
+      for (int k = 0; k < K; ++k) store_rows<NTS>(sp[k], m[k], nv, tid);
+      if (in) store_rows<NTS>(in, t, nv, tid);
+      const int i = (nv << 2) + tid;
+      if (i < ck.len) one(i);
+    } else {
+      for (int i = tid; i < ck.len; i += kThreads) one(i);
+    }
+  }
+};
+
 // Σ over n peers' copies of m slots (recv laid out [peer][slot]) -> averaged, re-quantised slots
 __global__ void __launch_bounds__(kThreads)
     k_q8_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,
@@ -262,6 +355,11 @@ hipError_t launch_unpack_sgd_q8(const Launch& L, const uint8_t* slots, float* ou
   if (a.momentum == 0.f) return run(L, UnpackSgdQ8<0>{slots, L.c0, outer, mom, a, inner_slot});
   if (a.first) return run(L, UnpackSgdQ8<1>{slots, L.c0, outer, mom, a, inner_slot});
   return run(L, UnpackSgdQ8<2>{slots, L.c0, outer, mom, a, inner_slot});
+}
+
+hipError_t launch_unpack_adamw_q8(const Launch& L, const uint8_t* slots, float* outer, float* m1,
+                                  float* m2, AdamArgs a, int inner_slot) {
+  return run(L, UnpackAdamWQ8{slots, L.c0, outer, AdamRule{m1, m2, a}, inner_slot});
 }
 
 hipError_t launch_q8_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get(
 )
 
 # constants mirrored from include/diloco_hip.h
-ABI_VERSION = 6
+ABI_VERSION = 7
 ALIGN_ELEMS = 64
 CHUNK_ELEMS = 4096
 ALL_BUCKETS = -1
@@ -112,6 +112,10 @@ SIGNATURES = {
     "dl_q8_reduce": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "dl_unpack_sgd_q8": (
         ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
+    ),
+    "dl_unpack_adamw_q8": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp],
     ),
     "dl_gather": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, _vp]),
     "dl_scatter": (ctypes.c_int, [_vp, _i32, _vp, _i32, _vp]),

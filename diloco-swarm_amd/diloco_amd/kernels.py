@@ -219,6 +219,15 @@ class HipKernels:
                   _ptr(mom), float(lr), float(momentum), int(nesterov), int(first),
                   int(inner_slot), _s(theta))
 
+    def unpack_adamw_q8(self, tree, bucket, slots, theta, exp_avg, exp_avg_sq, scalars,
+                        inner_slot) -> None:
+        """The averaged int8 slots of a bucket: g = q·s, then one AdamW step on θ, exp_avg,
+        exp_avg_sq (and the inner params), as unpack_adamw on the decoded values; scalars from
+        adamw_scalars."""
+        _lib.call("dl_unpack_adamw_q8", tree.handle, bucket, slots.data_ptr(), theta.data_ptr(),
+                  exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars, int(inner_slot),
+                  _s(theta))
+
     def unpack_avg(self, tree, bucket, wire, divisor, dst_slot, dst_packed=None) -> None:
         _lib.call("dl_unpack_avg", tree.handle, bucket, wire.data_ptr(), wire_code(wire.dtype),
                   int(divisor), int(dst_slot), _ptr(dst_packed), _s(wire))

@@ -1370,6 +1370,22 @@ class DeviceOuterMirror:
                                  momentum, nesterov, first, SLOT_INNER if write else -1)
         # the slots keep the average for a later .grad read (_xmode stays "q8")
 
+    def _q8_adamw(self, scalars, target) -> None:
+        """_q8_sgd under the AdamW rule: per bucket, wait for its all_gather, then
+        dl_unpack_adamw_q8 (g = q·s, AdamW on θ, exp_avg and exp_avg_sq, the inner params written
+        when the last delta's are bound). Every rank steps the whole tree."""
+        works, self._works = self._works, None
+        q = self._q8
+        write = target is not None
+        if write:
+            self.k.bind(self.tree, SLOT_INNER, target[0], self.device, key=tuple(target[1]))
+        for b in range(self.tree.n_buckets):
+            if works is not None:
+                works[b].wait()
+            self.k.unpack_adamw_q8(self.tree, b, self._q8_region(q, b), self.d_theta, self.d_m1,
+                                   self.d_m2, scalars, SLOT_INNER if write else -1)
+        # the slots keep the average for a later .grad read (_xmode stays "q8")
+
     def _launch_reductions(self, pack, view, group) -> None:
         """Fused N > 1: pack(b) then an asynchronous all_reduce(SUM) of bucket b, for every
         bucket, none waited for here (OuterSGD.step waits bucket by bucket, anything that reads
@@ -1482,9 +1498,8 @@ class DeviceOuterMirror:
     def adamw_ready(self) -> bool:
         """The fused AdamW pass covers what is pending: a recorded delta (one peer), the
         whole wire on this rank (replicated exchange, fp32 or bf16; eager mode), or this rank's
-        slices after the sharded / a2a exchange. Not the int8 slots: OuterAdamW then runs
-        torch's own step."""
-        return self._delta is not None or self._xmode in (None, "sharded", "a2a")
+        slices after the sharded / a2a exchange, or the averaged int8 slots (dl_unpack_adamw_q8)."""
+        return self._delta is not None or self._xmode in (None, "sharded", "a2a", "q8")
 
     def _adam_state(self, host_m, host_v):
         """The packed exp_avg / exp_avg_sq arenas holding the optimizer's state: zeros when it
@@ -1533,9 +1548,9 @@ class DeviceOuterMirror:
         arenas) for the optimizer state. One peer: dl_delta_pack_adamw (delta, .grad, AdamW, θ
         and the inner params); N > 1, replicated: dl_unpack_adamw per bucket, each waiting for
         its own collective, the pending /n left in the divisor; sharded / a2a: _sharded_adamw
-        on this rank's 1/n, after which exp_avg and exp_avg_sq hold this rank's slices."""
-        if not self.adamw_ready():
-            raise RuntimeError("adamw_step: the pending exchange is the int8 one")
+        on this rank's 1/n, after which exp_avg and exp_avg_sq hold this rank's slices; int8
+        wire: dl_unpack_adamw_q8 per bucket on the averaged slots (_q8_adamw), the whole tree
+        and the whole state on every rank."""
         self.settle_state()
         tver = self._theta_version()
         delta = self._take_delta(tver) if self._delta is not None else None
@@ -1544,6 +1559,7 @@ class DeviceOuterMirror:
             self._relay_grads(zero_fill_missing=False)
         bufs = self._adam_state(host_m, host_v)
         sharded = delta is None and self._xmode in ("sharded", "a2a")
+        q8 = delta is None and self._xmode == "q8"
         if self._adam_stale and not (
                 sharded and self._adam_shard == (self._xgroup, self._xn, self._xrank)):
             self.gather_adam_state()  # a whole-tree pass needs every slice of the state
@@ -1554,6 +1570,8 @@ class DeviceOuterMirror:
                                     self.d_m1, self.d_m2, scalars)
         elif sharded:  # N > 1, sharded / a2a exchange: this rank's 1/n, then all_gather(θ)
             self._sharded_adamw(scalars, target)
+        elif q8:  # N > 1, int8 wire: the averaged slots of each bucket, AdamW fused in
+            self._q8_adamw(scalars, target)
         else:
             if write:
                 self.k.bind(self.tree, SLOT_INNER, target[0], self.device, key=tuple(target[1]))

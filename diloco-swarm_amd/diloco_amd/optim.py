@@ -117,7 +117,8 @@ class OuterAdamW(AdamW):
     the replicated exchange; after the sharded exchange (asked for: exchange="sharded") one
     dl_shard_adamw per bucket on this rank's 1/n, after the rank-order one
     (DILOCO_DP_EXCHANGE=a2a, bit-exact at every replica count) one dl_shard_reduce_adamw, each
-    followed by the all_gather of θ. It IS a torch.optim.AdamW (param_groups, hooks, LR
+    followed by the all_gather of θ; after the int8 exchange (wire="int8") one
+    dl_unpack_adamw_q8 per bucket on the averaged slots, the whole tree on every rank. It IS a torch.optim.AdamW (param_groups, hooks, LR
     schedulers and state_dict work unchanged; state[p]["step"] is torch's fp32 scalar tensor,
     exp_avg and exp_avg_sq are views of the mirror's packed arenas), selected by get_optimizer
     under DILOCO_OUTER_ADAMW=fused. After a sharded or rank-order step each rank holds its own
@@ -127,8 +128,7 @@ class OuterAdamW(AdamW):
     The fused pass is one element of torch's _single_tensor_adamw (include/diloco_hip.h).
     Whenever that contract or the mirror does not cover the step -- amsgrad, maximize,
     capturable, differentiable, beta1 <= 0.5, tensor hyper-parameters, more than one group,
-    parameters whose step counts differ, the int8 exchange, write_back "sync" or
-    "deferred", no mirror at all (a CPU-only run) -- step() runs torch's own step body, exactly
+    parameters whose step counts differ, write_back "sync" or "deferred", no mirror at all (a CPU-only run) -- step() runs torch's own step body, exactly
     what a stock AdamW on this outer model does: never a silently different result."""
 
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas=(0.9, 0.999),

@@ -20,8 +20,9 @@ step is one dl_delta_pack_adamw pass at one peer (36 B/param) and one dl_unpack_
 bucket at N > 1; an outer model it is attached to takes the replicated exchange when none was
 asked for. Asked for, the sharded exchange steps this rank's 1/n with dl_shard_adamw and the
 rank-order one (DILOCO_DP_EXCHANGE=a2a) with dl_shard_reduce_adamw, exp_avg and exp_avg_sq
-staying sharded until read. Anything its kernels do not cover (the int8 wire; see
-optim.OuterAdamW) runs torch's own step.
+staying sharded until read. On the int8 wire (DILOCO_OUTER_WIRE=int8) every rank steps the whole
+tree from the averaged slots, one dl_unpack_adamw_q8 pass per bucket. Anything its kernels do
+not cover (amsgrad, tensor hyper-parameters, ...; see optim.OuterAdamW) runs torch's own step.
 
 The inner optimizer (AdamW on a model that is not an outer model) is stock torch.optim.AdamW
 unless DILOCO_INNER_ADAMW=fused: then get_optimizer returns optim.InnerAdamW, whose step is one

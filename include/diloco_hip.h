@@ -30,7 +30,7 @@ extern "C" {
 
 #define DL_API __attribute__((visibility("default")))
 
-#define DL_ABI_VERSION 6
+#define DL_ABI_VERSION 7
 #define DL_ALIGN_ELEMS 64      /* segment start alignment in the packed space: 256 B of fp32 */
 #define DL_CHUNK_ELEMS 4096    /* work unit of every segment walker: 16 KiB of fp32 */
 #define DL_ALL_BUCKETS (-1)
@@ -104,7 +104,7 @@ DL_API int dl_tree_bind(dl_tree_t tree, int32_t slot, const uint64_t* dev_ptrs, 
 /* Launch shape of every walker kernel on this tree: max_blocks caps the grid (0 = one
  * workgroup per chunk, the default); flags = DL_TUNE_AUTO (the default: the measured
  * per-kernel choice -- NT loads everywhere; NT stores in the SGD kernels, dl_scatter,
- * dl_unpack_avg and dl_unpack_sgd_q8, and in dl_delta_pack / dl_gather over launches of more
+ * dl_unpack_avg, dl_unpack_sgd_q8 and dl_unpack_adamw_q8, and in dl_delta_pack / dl_gather over launches of more
  * than 2^28 elements; plain stores for those two producers below that size, where the next
  * kernel or RCCL re-reads their output from the Infinity Cache) or DL_TUNE_NT_LOADS [|
  * DL_TUNE_NT_STORES] for every kernel. Plain loads, DL_TUNE_WT_STORES (write-through, sc1)
@@ -363,7 +363,8 @@ DL_API int dl_shard_reduce_adamw(const void* slices, int32_t wire_dtype, int32_t
  * dl_delta_q8:      slots <- quantise(outer - inner) per chunk  (a2, 8 B read + 1.02 B written)
  * dl_q8_reduce:     out[j] <- quantise((sum_r deq(recv[r][j])) / divisor), r in rank order;
  *                   recv holds n_peers x n_slots slots; out may alias recv when n_peers == 1
- * dl_unpack_sgd_q8: g = deq(slot); SGD and copy-back exactly as dl_unpack_sgd (divisor 1). */
+ * dl_unpack_sgd_q8: g = deq(slot); SGD and copy-back exactly as dl_unpack_sgd (divisor 1).
+ * dl_unpack_adamw_q8: the AdamW twin of dl_unpack_sgd_q8, below. */
 DL_API int dl_delta_q8(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
                        const float* outer_packed, void* slots, dl_stream_t stream);
 DL_API int dl_q8_reduce(const void* recv, int32_t n_peers, int32_t n_slots, int32_t divisor,
@@ -372,6 +373,24 @@ DL_API int dl_unpack_sgd_q8(dl_tree_t tree, int32_t bucket, const void* slots,
                             float* outer_packed, float* mom_packed, float lr, float momentum,
                             int32_t nesterov, int32_t first_step, int32_t inner_slot,
                             dl_stream_t stream);
+/* a4+a5 for an AdamW outer optimizer after the int8 exchange: one pass over the averaged slots
+ * of a bucket (slot of chunk c at (c - first chunk of the bucket) * DL_Q8_SLOT_BYTES; the
+ * whole tree with DL_ALL_BUCKETS). Per element k of the packed space:
+ *   g = float(int8 q) * s                 (one rounded fp32 multiply: the product
+ *                                          dl_unpack_sgd_q8 forms, the decoded .grad value)
+ *   one element of dl_unpack_adamw's arithmetic (divisor 1), its seven scalars in its order,
+ *   on θ = outer[k], m = exp_avg[k], v = exp_avg_sq[k];  inner[seg][j] = θ
+ * so it is bit-identical to decoding the slots into an fp32 wire and running dl_unpack_adamw
+ * on it. The slots are only read. inner_slot < 0 skips the inner write. Nothing is stored
+ * past a chunk's length: the padding of the packed buffers is never written. Results do not
+ * depend on the inner tensors' alignment, the grid or the bucket split. slots, outer and both
+ * state pointers non-null and 16-B aligned. 29.02 B/param: 1.016 + 12 read, 12 + 4 written
+ * (25.02 without the inner write). */
+DL_API int dl_unpack_adamw_q8(dl_tree_t tree, int32_t bucket, const void* slots,
+                              float* outer_packed, float* exp_avg_packed,
+                              float* exp_avg_sq_packed, float decay, float w1, float beta2,
+                              float w2, float neg_step_size, float bc2_sqrt, float eps,
+                              int32_t inner_slot, dl_stream_t stream);
 
 /* ---- serializer (src/serializer.py:11-15) ----------------------------------------------
  * out is fp32 of 2*numel elements: out[0] = meta0, out[1] = meta1, out[numel + i] =
