@@ -927,9 +927,38 @@ DL_API int dl_q8_reduce(const void* recv, int32_t n, int32_t m, int32_t divisor,
   DL_TRY(check_packed(recv, "dl_q8_reduce", "recv"));
   DL_TRY(check_packed(out, "dl_q8_reduce", "out"));
   if (recv == out && n != 1) return fail(DL_E_ARG, "dl_q8_reduce: in place needs n_peers == 1");
-  hipError_t e = dl::launch_q8_reduce(static_cast<const uint8_t*>(recv), n, m, divisor,
+  hipError_t e = dl::launch_q8_reduce(static_cast<const uint8_t*>(recv), n, m, divisor, nullptr,
                                       static_cast<uint8_t*>(out), static_cast<hipStream_t>(s));
   return e == hipSuccess ? DL_OK : hip_fail(e, "dl_q8_reduce");
+}
+
+// dl_delta_q8 with the encoder's residual: the same launch and policy (the residual is read
+// once and rewritten once per outer step, as streaming as the payload)
+DL_API int dl_delta_q8_ef(dl_tree_t t, int32_t b, int32_t inner_slot, const float* outer,
+                          float* residual, void* slots, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_delta_q8_ef", kAutoDeltaQ8));
+  DL_TRY(check_slot(t, inner_slot, "dl_delta_q8_ef"));
+  DL_TRY(check_packed(outer, "dl_delta_q8_ef", "outer"));
+  DL_TRY(check_packed(residual, "dl_delta_q8_ef", "residual"));
+  DL_TRY(check_packed(slots, "dl_delta_q8_ef", "slots"));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_delta_q8_ef"));
+  hipError_t e = dl::launch_delta_q8_ef(L, inner_slot, outer, residual, static_cast<uint8_t*>(slots));
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_q8_ef")
+                         : hip_fail(e, "dl_delta_q8_ef");
+}
+
+DL_API int dl_q8_reduce_ef(const void* recv, int32_t n, int32_t m, int32_t divisor,
+                           float* residual, void* out, dl_stream_t s) {
+  if (n < 1 || m < 0 || divisor < 1)
+    return fail(DL_E_ARG, "dl_q8_reduce_ef: n %d m %d div %d", n, m, divisor);
+  DL_TRY(check_packed(recv, "dl_q8_reduce_ef", "recv"));
+  DL_TRY(check_packed(residual, "dl_q8_reduce_ef", "residual"));
+  DL_TRY(check_packed(out, "dl_q8_reduce_ef", "out"));
+  if (recv == out && n != 1) return fail(DL_E_ARG, "dl_q8_reduce_ef: in place needs n_peers == 1");
+  hipError_t e = dl::launch_q8_reduce(static_cast<const uint8_t*>(recv), n, m, divisor, residual,
+                                      static_cast<uint8_t*>(out), static_cast<hipStream_t>(s));
+  return e == hipSuccess ? DL_OK : hip_fail(e, "dl_q8_reduce_ef");
 }
 
 DL_API int dl_unpack_sgd_q8(dl_tree_t t, int32_t b, const void* slots, float* outer, float* mom,

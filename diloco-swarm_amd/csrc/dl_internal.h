@@ -93,12 +93,15 @@ hipError_t launch_slices_sgd(const void* slices, int wire_dtype, int32_t n, int6
                              float* outer, float* mom, SgdArgs a, hipStream_t s,
                              bool avg_only = false);
 hipError_t launch_delta_q8(const Launch& L, int inner_slot, const float* outer, uint8_t* slots);
+hipError_t launch_delta_q8_ef(const Launch& L, int inner_slot, const float* outer, float* resid,
+                              uint8_t* slots);
 hipError_t launch_unpack_sgd_q8(const Launch& L, const uint8_t* slots, float* outer, float* mom,
                                 SgdArgs a, int inner_slot);
 hipError_t launch_unpack_adamw_q8(const Launch& L, const uint8_t* slots, float* outer, float* m1,
                                   float* m2, AdamArgs a, int inner_slot);
+// resid: the owner's stage-2 residual (dl_q8_reduce_ef), or nullptr (dl_q8_reduce)
 hipError_t launch_q8_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,
-                            uint8_t* out, hipStream_t s);
+                            float* resid, uint8_t* out, hipStream_t s);
 hipError_t launch_unpack_adamw(const Launch& L, const void* wire, int wire_dtype, int divisor,
                                float* outer, float* m1, float* m2, AdamArgs a, int inner_slot);
 hipError_t launch_delta_pack_adamw(const Launch& L, int inner_slot, float* outer, void* wire,

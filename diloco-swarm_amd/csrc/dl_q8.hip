@@ -14,6 +14,16 @@
 //                     exp_avg_sq exactly as dl_unpack_adamw (divisor 1); inner = θ
 // Quantiser: s = amax / 127 (IEEE division); q = s == 0 ? 0 : clamp(rint(x / s), -127, 127);
 // dequantised value q·s. Bus bytes per peer 2(n-1)/n · 1.016 B/param vs 8(n-1)/n for fp32.
+//
+// Error feedback (off by default): both lossy stages can carry what rounding removed into the
+// next outer step, so an element that stays below s/2 of its chunk is sent late, not never:
+//   dl_delta_q8_ef    x = (θ - inner) + r; slot <- quantise(x); r <- x - q·s   (r: fp32, packed)
+//   dl_q8_reduce_ef   x = avg + r2;        slot <- quantise(x); r2 <- x - q·s  (r2: the owner's
+//                     n_slots · DL_CHUNK_ELEMS floats)
+// q·s is the product the unpack kernels decode, so r is exactly what the receiver did not get.
+// The residuals stay local; every peer still receives byte-identical averaged slots. Non-finite
+// values get no special case: a NaN/Inf element of x leaves a NaN/Inf residual (IEEE rules)
+// until the residual is reset.
 #include "dl_outer_step.h"
 
 namespace dl {
@@ -77,11 +87,31 @@ typedef DL_GLOBAL const uint32_t* gcu32;
 // profiles/r02_q8_layout.txt).
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
+// EF: x = d + r replaces d, and r <- x - q·s is written back in place by the lane that read it
+// (12 B read, 1.016 + 4 B written per param against 8 + 1.016); nothing of r is touched past the
+// chunk's length. Every global load (θ, inner, r) is issued before the amax reduction.
+__device__ __forceinline__ float resid1(float x, float s) { return x - float(q8(x, s)) * s; }
+__device__ __forceinline__ float4 resid4(float4 x, float s) {
+  return make_float4(resid1(x.x, s), resid1(x.y, s), resid1(x.z, s), resid1(x.w, s));
+}
+__device__ __forceinline__ float4 add4(float4 a, float4 b) {
+  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+
+template <bool EF>
 struct DeltaQ8 {
   int inner_slot;
   const float* outer;
   uint8_t* slots;  // slot of chunk c at (c - c0) * DL_Q8_SLOT_BYTES
   int c0;
+  float* resid;  // EF: the packed residual arena
+  // the value to quantise, 16 B per stream: θ - inner, + r with error feedback
+  template <bool NTL>
+  static __device__ __forceinline__ float4 x4(const float* th, const float* in, const float* rs, int v) {
+    const float4 d = sub4(ldf4<NTL>(th, v), ldf4<NTL>(in, v));
+    if constexpr (EF) return add4(d, ldf4<NTL>(rs, v));
+    else return d;
+  }
   template <bool NTL, int NTS>
   __device__ __forceinline__ void run(const Chunk& ck, int c, void* const* caddr, int nchunk, int tid) const {
     __shared__ u32x4 stage[DL_CHUNK_ELEMS / 16];  // the payload, 16 B per lane
@@ -89,6 +119,7 @@ struct DeltaQ8 {
     uint8_t* st8 = reinterpret_cast<uint8_t*>(stage);
     const float* in = slot_ptr<const float>(caddr, nchunk, inner_slot, c);
     const float* th = outer + ck.poff;
+    float* rs = EF ? resid + ck.poff : nullptr;
     uint8_t* slot = slots + size_t(c - c0) * DL_Q8_SLOT_BYTES;
     const int nv = ck.len >> 2;
     const bool vec = aligned16(in);
@@ -100,11 +131,11 @@ struct DeltaQ8 {
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int v = u * kThreads + tid;
-        d[u] = v < nv ? sub4(ldf4<NTL>(th, v), ldf4<NTL>(in, v)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        d[u] = v < nv ? x4<NTL>(th, in, rs, v) : make_float4(0.f, 0.f, 0.f, 0.f);
         am = fmaxf(am, amax4(d[u]));
       }
       const int i = (nv << 2) + tid;
-      if (i < ck.len) dt = th[i] - in[i];
+      if (i < ck.len) dt = EF ? (th[i] - in[i]) + rs[i] : th[i] - in[i];
     } else {  // 4-B-aligned tensor storage: element k*256 + tid of the chunk in d[k/4].k%4
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
@@ -112,7 +143,7 @@ struct DeltaQ8 {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int i = (4 * u + j) * kThreads + tid;
-          e[j] = i < ck.len ? th[i] - in[i] : 0.f;
+          e[j] = i < ck.len ? (EF ? (th[i] - in[i]) + rs[i] : th[i] - in[i]) : 0.f;
         }
         d[u] = make_float4(e[0], e[1], e[2], e[3]);
         am = fmaxf(am, amax4(d[u]));
@@ -124,10 +155,16 @@ struct DeltaQ8 {
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int v = u * kThreads + tid;
-        if (v < nv) st32[v] = pack4(d[u], s);
+        if (v < nv) {
+          st32[v] = pack4(d[u], s);
+          if constexpr (EF) stf4<NTS>(rs, v, resid4(d[u], s));
+        }
       }
       const int i = (nv << 2) + tid;
-      if (i < ck.len) st8[i] = uint8_t(q8(dt, s));
+      if (i < ck.len) {
+        st8[i] = uint8_t(q8(dt, s));
+        if constexpr (EF) rs[i] = resid1(dt, s);
+      }
     } else {
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
@@ -135,7 +172,10 @@ struct DeltaQ8 {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int i = (4 * u + j) * kThreads + tid;
-          if (i < ck.len) st8[i] = uint8_t(q8(e[j], s));
+          if (i < ck.len) {
+            st8[i] = uint8_t(q8(e[j], s));
+            if constexpr (EF) rs[i] = resid1(e[j], s);
+          }
         }
       }
     }
@@ -308,14 +348,21 @@ struct UnpackAdamWQ8 {
 };
 
 // Σ over n peers' copies of m slots (recv laid out [peer][slot]) -> averaged, re-quantised slots
+// EF: the owner's residual r2 (m · DL_CHUNK_ELEMS floats) is added to the average before the
+// quantiser and rewritten by the same lane; a zero slot keeps a zero residual (x = q = r2 = 0).
+template <bool EF>
 __global__ void __launch_bounds__(kThreads)
-    k_q8_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,
+    k_q8_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor, float* resid,
                 uint8_t* out) {  // recv == out at one peer (in place): no __restrict__
   const int j = blockIdx.x;
   const int tid = threadIdx.x;
-  float4 acc[kUnroll];
+  float* rs = EF ? resid + size_t(j) * DL_CHUNK_ELEMS : nullptr;
+  float4 acc[kUnroll], r2[kUnroll];
 #pragma unroll
-  for (int u = 0; u < kUnroll; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int u = 0; u < kUnroll; ++u) {
+    acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (EF) r2[u] = ldf4<true>(rs, u * kThreads + tid);
+  }
   for (int r = 0; r < n; ++r) {  // rank order: the sum is identical on every peer
     const uint8_t* slot = recv + (size_t(r) * m + j) * DL_Q8_SLOT_BYTES;
     const float s = *reinterpret_cast<const float*>(slot);
@@ -330,6 +377,7 @@ __global__ void __launch_bounds__(kThreads)
 #pragma unroll
   for (int u = 0; u < kUnroll; ++u) {
     if (divisor > 1) acc[u] = div4(acc[u], float(divisor));
+    if constexpr (EF) acc[u] = add4(acc[u], r2[u]);
     am = fmaxf(am, amax4(acc[u]));
   }
   const float s = block_amax(am) / 127.f;
@@ -337,7 +385,10 @@ __global__ void __launch_bounds__(kThreads)
   __shared__ u32x4 stage[DL_CHUNK_ELEMS / 16];
   uint32_t* st32 = reinterpret_cast<uint32_t*>(stage);
 #pragma unroll
-  for (int u = 0; u < kUnroll; ++u) st32[u * kThreads + tid] = pack4(acc[u], s);
+  for (int u = 0; u < kUnroll; ++u) {
+    st32[u * kThreads + tid] = pack4(acc[u], s);
+    if constexpr (EF) stf4<kStNT>(rs, u * kThreads + tid, resid4(acc[u], s));
+  }
   __syncthreads();
   uint8_t* o = out + size_t(j) * DL_Q8_SLOT_BYTES;
   __builtin_nontemporal_store(stage[tid], (DL_GLOBAL u32x4*)(o + kQ8Header) + tid);
@@ -347,7 +398,12 @@ __global__ void __launch_bounds__(kThreads)
 }  // namespace
 
 hipError_t launch_delta_q8(const Launch& L, int inner_slot, const float* outer, uint8_t* slots) {
-  return run(L, DeltaQ8{inner_slot, outer, slots, L.c0});
+  return run(L, DeltaQ8<false>{inner_slot, outer, slots, L.c0, nullptr});
+}
+
+hipError_t launch_delta_q8_ef(const Launch& L, int inner_slot, const float* outer, float* resid,
+                              uint8_t* slots) {
+  return run(L, DeltaQ8<true>{inner_slot, outer, slots, L.c0, resid});
 }
 
 hipError_t launch_unpack_sgd_q8(const Launch& L, const uint8_t* slots, float* outer, float* mom,
@@ -363,9 +419,14 @@ hipError_t launch_unpack_adamw_q8(const Launch& L, const uint8_t* slots, float* 
 }
 
 hipError_t launch_q8_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,
-                            uint8_t* out, hipStream_t s) {
+                            float* resid, uint8_t* out, hipStream_t s) {
   if (m <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_q8_reduce, dim3(m), dim3(kThreads), 0, s, recv, n, m, divisor, out);
+  if (resid)
+    hipLaunchKernelGGL(k_q8_reduce<true>, dim3(m), dim3(kThreads), 0, s, recv, n, m, divisor,
+                       resid, out);
+  else
+    hipLaunchKernelGGL(k_q8_reduce<false>, dim3(m), dim3(kThreads), 0, s, recv, n, m, divisor,
+                       resid, out);
   return hipGetLastError();
 }
 

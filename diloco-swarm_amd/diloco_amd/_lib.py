@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get(
 )
 
 # constants mirrored from include/diloco_hip.h
-ABI_VERSION = 7
+ABI_VERSION = 8
 ALIGN_ELEMS = 64
 CHUNK_ELEMS = 4096
 ALL_BUCKETS = -1
@@ -110,6 +110,8 @@ SIGNATURES = {
     ),
     "dl_delta_q8": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "dl_q8_reduce": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "dl_delta_q8_ef": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "dl_q8_reduce_ef": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dl_unpack_sgd_q8": (
         ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
     ),

@@ -213,6 +213,18 @@ class HipKernels:
         _lib.call("dl_q8_reduce", recv.data_ptr(), int(n_peers), int(n_slots), int(divisor),
                   out.data_ptr(), _s(out))
 
+    def delta_q8_ef(self, tree, bucket, inner_slot, theta, residual, slots) -> None:
+        """delta_q8 with error feedback: x = (θ - inner) + residual is quantised and
+        residual <- x - q·s in place (fp32, the tree's packed layout)."""
+        _lib.call("dl_delta_q8_ef", tree.handle, bucket, inner_slot, theta.data_ptr(),
+                  residual.data_ptr(), slots.data_ptr(), _s(theta))
+
+    def q8_reduce_ef(self, recv, n_peers, n_slots, divisor, residual, out) -> None:
+        """q8_reduce with the shard owner's residual (n_slots * CHUNK_ELEMS floats) added to the
+        average before it is re-quantised, and rewritten in place."""
+        _lib.call("dl_q8_reduce_ef", recv.data_ptr(), int(n_peers), int(n_slots), int(divisor),
+                  residual.data_ptr(), out.data_ptr(), _s(out))
+
     def unpack_sgd_q8(self, tree, bucket, slots, theta, mom, lr, momentum, nesterov, first,
                       inner_slot) -> None:
         _lib.call("dl_unpack_sgd_q8", tree.handle, bucket, slots.data_ptr(), theta.data_ptr(),

@@ -645,7 +645,8 @@ class DeviceOuterMirror:
 
     def __init__(self, outer_model: torch.nn.Module, device: torch.device, kernels=None,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = False,
-                 wire: str = "f32", exchange: str = "sharded", keep_params: bool = False):
+                 wire: str = "f32", exchange: str = "sharded", keep_params: bool = False,
+                 error_feedback: bool = False):
         """keep_params: the outer model's Parameter objects stay the ones it has (their class
         switched to OuterParameter in place) -- for an outer model that got its device only
         at its first compute_pseudo_gradient, after get_optimizer took references to them.
@@ -656,6 +657,14 @@ class DeviceOuterMirror:
             raise ValueError(f"wire {wire!r}: one of {OUTER_WIRES}")
         if exchange not in OUTER_EXCHANGES:
             raise ValueError(f"exchange {exchange!r}: one of {OUTER_EXCHANGES}")
+        if error_feedback and wire != "int8":
+            raise ValueError("error_feedback compensates the int8 wire's quantiser; it needs "
+                             "wire='int8'")
+        # int8 wire: every encode carries its residual (dl_delta_q8_ef) and the re-quantised
+        # average the owner's (dl_q8_reduce_ef); the arenas are made at the first exchange
+        self.error_feedback = bool(error_feedback)
+        self._q8_res: Optional[torch.Tensor] = None
+        self._q8_res_load: Optional[list] = None  # a loaded stage-2 state, until the buffers exist
         self.exchange = exchange
         self.params: List[torch.nn.Parameter] = module_params(outer_model)
         if not self.params:
@@ -1255,7 +1264,9 @@ class DeviceOuterMirror:
     def _q8_buffers(self, n: int) -> dict:
         """Slot regions of every bucket (n·m slots of Q8_SLOT bytes: the bucket's chunks in
         order, zero padding to a multiple of n), two all_to_all landing buffers, one reduced
-        region per bucket (so every bucket's all_gather may stay in flight)."""
+        region per bucket (so every bucket's all_gather may stay in flight). Error feedback:
+        the stage-2 residual of the reduced regions, zero whenever the buffers are (re)built
+        for another peer count, unless a loaded state of this layout waits for them."""
         q = getattr(self, "_q8", None)
         if q is not None and q["n"] == n:
             return q
@@ -1276,7 +1287,68 @@ class DeviceOuterMirror:
                         "slots": torch.zeros(base * Q8_SLOT, **z),
                         "red": torch.zeros(rbase * Q8_SLOT, **z),
                         "recv": [torch.zeros(n * mmax * Q8_SLOT, **z) for _ in range(2)]}
+        if self.error_feedback:
+            q["res"] = torch.zeros(rbase * S_CHUNK, dtype=torch.float32, device=self.device)
+            load, self._q8_res_load = self._q8_res_load, None
+            if load is not None:
+                self._q8_set_reduce_state(load)
         return q
+
+    def _q8_reduce_residual(self, q: dict, b: int) -> torch.Tensor:
+        _nch, m, _base, rb = q["plan"][b]
+        return q["res"][rb * S_CHUNK:(rb + m) * S_CHUNK]
+
+    def _q8_set_reduce_state(self, state: list) -> None:
+        q = self._q8
+        dst = [self._q8_reduce_residual(q, b) for b in range(len(q["plan"]))]
+        if len(state) != len(dst) or any(tuple(a.shape) != tuple(d.shape)
+                                          for a, d in zip(state, dst)):
+            raise ValueError("the int8 error-feedback state does not match this exchange's "
+                             "buckets and peer count")
+        for d, a in zip(dst, state):
+            d.copy_(a)
+
+    def q8_ef_state(self) -> Optional[dict]:
+        """{"encode": the encoder's residual, "reduce": [this peer's stage-2 residual per
+        bucket]} as clones; None when error feedback is off or no exchange has run yet."""
+        if not self.error_feedback or self._q8_res is None:
+            return None
+        self._join()
+        q = getattr(self, "_q8", None)
+        if q is not None:
+            red = [self._q8_reduce_residual(q, b).clone() for b in range(len(q["plan"]))]
+        else:
+            red = [a.clone() for a in (self._q8_res_load or [])]
+        return {"encode": self._q8_res.clone(), "reduce": red}
+
+    def load_q8_ef_state(self, state: Optional[dict]) -> None:
+        """Copy a q8_ef_state() back (None: reset every residual to zero)."""
+        if not self.error_feedback:
+            if state is None:
+                return
+            raise ValueError("this outer model runs without int8 error feedback")
+        self._join()
+        z = dict(dtype=torch.float32, device=self.device)
+        q = getattr(self, "_q8", None)
+        if state is None:
+            if self._q8_res is not None:
+                self._q8_res.zero_()
+            if q is not None:
+                q["res"].zero_()
+            self._q8_res_load = None
+            return
+        enc = state["encode"]
+        if tuple(enc.shape) != (self.tree.total,):
+            raise ValueError(f"int8 error-feedback state: encode residual of {tuple(enc.shape)}, "
+                             f"expected ({self.tree.total},)")
+        red = [a.to(**z) for a in state["reduce"]]
+        if q is not None:
+            self._q8_set_reduce_state(red)
+        else:
+            self._q8_res_load = red
+        if self._q8_res is None:
+            self._q8_res = torch.zeros(self.tree.total, **z)
+        self._q8_res.copy_(enc)
 
     def _q8_region(self, q: dict, b: int) -> torch.Tensor:
         nch, m, base, _ = q["plan"][b]
@@ -1288,7 +1360,9 @@ class DeviceOuterMirror:
         order, / n, re-quantised) -> all_gather of the averaged slots, left in flight (the
         next bucket's pack and all_to_all are issued before this one's reduce). Fused: the SGD
         pass dequantises inside dl_unpack_sgd_q8; .grad shows the decoded average when read.
-        Eager: decoded into .grad at once."""
+        Eager: decoded into .grad at once. With error feedback both kernels are their _ef
+        forms: every encode (either path) carries this rank's residual, the reduce its owner's;
+        the slots, and so the optimizer passes and .grad, are used as without it."""
         if self._delta is not None:
             self._take_delta()
             self._relay_theta()
@@ -1308,9 +1382,15 @@ class DeviceOuterMirror:
             theta, slot = self.d_wire, SLOT_AUX
         q = self._q8_buffers(n)
         S, nb = q["S"], self.tree.n_buckets
+        ef = self.error_feedback
+        if ef and self._q8_res is None:
+            self._q8_res = torch.zeros(self.tree.total, dtype=torch.float32, device=self.device)
 
         def pack(b):
-            self.k.delta_q8(self.tree, b, slot, theta, self._q8_region(q, b))
+            if ef:  # both encode paths carry the residual
+                self.k.delta_q8_ef(self.tree, b, slot, theta, self._q8_res, self._q8_region(q, b))
+            else:
+                self.k.delta_q8(self.tree, b, slot, theta, self._q8_region(q, b))
 
         def a2a(b):
             nch, m, _, _ = q["plan"][b]
@@ -1327,7 +1407,11 @@ class DeviceOuterMirror:
             pend[b].wait()
             nch, m, _, rb = q["plan"][b]
             red = q["red"][rb * S:(rb + m) * S]
-            self.k.q8_reduce(q["recv"][b % 2][:n * m * S], n, m, n, red)
+            if ef:
+                self.k.q8_reduce_ef(q["recv"][b % 2][:n * m * S], n, m, n,
+                                    self._q8_reduce_residual(q, b), red)
+            else:
+                self.k.q8_reduce(q["recv"][b % 2][:n * m * S], n, m, n, red)
             works[b] = dist.all_gather_into_tensor(self._q8_region(q, b), red, group=group,
                                                    async_op=True)
         self._works = works
@@ -1805,7 +1889,8 @@ class LazyHostOuterMirror:
 
     def __init__(self, outer_model: torch.nn.Module, device: torch.device, kernels=None,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = True,
-                 wire: str = "f32", exchange: str = DEFAULT_EXCHANGE["host"]):
+                 wire: str = "f32", exchange: str = DEFAULT_EXCHANGE["host"],
+                 error_feedback: bool = False):
         self.device = torch.device(device)
         params = module_params(outer_model)
         if not params:
@@ -1817,7 +1902,7 @@ class LazyHostOuterMirror:
                 torch.nn.Parameter(_DATA.__get__(p).to(self.device), p.requires_grad)
                 for p in params])
         self.dev = DeviceOuterMirror(twin, self.device, kernels, bucket_cap_elems, fused, wire,
-                                     exchange)
+                                     exchange, error_feedback=error_feedback)
         self._twin = twin
         self.fused, self.wire, self.exchange = fused, wire, exchange
         from .utils import env_flag

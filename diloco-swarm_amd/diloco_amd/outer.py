@@ -23,6 +23,9 @@ Exchange variants, all bucketed and pipelined across buckets:
   replicated         (shard=False; the bf16 wire's default) RCCL all-reduce -> dl_unpack_sgd
                      (/n + SGD + copy-back, 24 B/param) on every replica
   int8 wire          dl_delta_q8 -> all_to_all -> dl_q8_reduce -> all_gather -> dl_unpack_sgd_q8
+                     error_feedback=True: dl_delta_q8_ef and dl_q8_reduce_ef in their places --
+                     what each quantiser rounds away is added to the next outer step's value
+                     (q_residual, 4P; q_residual_red, 4P/n; both stay on this peer)
   direct (xgmi)      exchange="xgmi": IPC-mapped peers, one dl_xgmi_reduce_sgd per rank;
                      exchange="xgmi_inner": no wire -- the inner params live in one packed
                      arena the peers read, dl_xgmi_delta_sgd forms θ - inner_q itself
@@ -121,6 +124,7 @@ class OuterSync:
         exchange: str = "rccl",
         tile_chunks: int = DEFAULT_TILE_CHUNKS,
         keep_wire: bool = False,
+        error_feedback: bool = False,
     ):
         self._objs = list(params)  # the caller's objects (exchange="xgmi_inner" relays them)
         self.params: List[torch.Tensor] = [p.data if isinstance(p, torch.nn.Parameter) else p
@@ -153,6 +157,12 @@ class OuterSync:
         if wire_dtype not in (torch.float32, torch.bfloat16, torch.int8):
             raise ValueError(f"wire dtype {wire_dtype}: float32, bfloat16 or int8")
         self.q8 = wire_dtype == torch.int8
+        # int8 wire only: carry what each quantiser rounds away into the next outer step
+        # (dl_delta_q8_ef, dl_q8_reduce_ef)
+        self.error_feedback = bool(error_feedback)
+        if self.error_feedback and not self.q8:
+            raise ValueError("error_feedback compensates the int8 wire's quantiser; it needs "
+                             "wire_dtype=torch.int8")
         shard_given = shard
         if shard is None:
             # fp32 wire: same bus bytes as the all-reduce, fewer HBM bytes. bf16 wire: the
@@ -206,6 +216,15 @@ class OuterSync:
             self.q_slots = torch.zeros(base * Q8_SLOT, dtype=torch.uint8, **z)
             self.q_recv = torch.zeros(n * mmax * Q8_SLOT, dtype=torch.uint8, **z)
             self.q_red = torch.zeros(mmax * Q8_SLOT, dtype=torch.uint8, **z)
+            # error feedback: the encoder's residual in the packed layout, and at n > 1 the
+            # residual of this peer's m_b re-quantised slots of every bucket
+            self.q_residual = self.q_residual_red = None
+            if self.error_feedback:
+                self.q_residual = torch.zeros(self.tree.total, dtype=torch.float32, **z)
+                if n > 1:
+                    self.q_residual_red = [
+                        torch.zeros(m * _lib.CHUNK_ELEMS, dtype=torch.float32, **z)
+                        for _nch, m, _base in self.q8_plan]
         elif self.xgmi_inner:
             self.wire = None
         else:
@@ -295,9 +314,15 @@ class OuterSync:
                                "the pseudo-gradient; use step()")
         self._bind_inner()
         if self.q8:
-            self.k.delta_q8(self.tree, bucket, SLOT_INNER, self.theta, self.q8_region(bucket))
+            self._delta_q8(bucket, self.q8_region(bucket))
         else:
             self.k.delta_pack(self.tree, bucket, SLOT_INNER, self.theta, self.wire)
+
+    def _delta_q8(self, bucket: int, slots: torch.Tensor) -> None:
+        if self.error_feedback:
+            self.k.delta_q8_ef(self.tree, bucket, SLOT_INNER, self.theta, self.q_residual, slots)
+        else:
+            self.k.delta_q8(self.tree, bucket, SLOT_INNER, self.theta, slots)
 
     def q8_region(self, bucket: int) -> torch.Tensor:
         """The int8 slots of one bucket (n * m slots, chunk order, zero padding at the end)."""
@@ -317,7 +342,10 @@ class OuterSync:
         recv = self.q_recv[:n * m * Q8_SLOT]
         dist.all_to_all_single(recv, region, group=self.group, async_op=True).wait()
         red = self.q_red[:m * Q8_SLOT]
-        self.k.q8_reduce(recv, n, m, n, red)
+        if self.error_feedback:
+            self.k.q8_reduce_ef(recv, n, m, n, self.q_residual_red[bucket], red)
+        else:
+            self.k.q8_reduce(recv, n, m, n, red)
         return dist.all_gather_into_tensor(region, red, group=self.group, async_op=True)
 
     # ---- sharded variant --------------------------------------------------------
@@ -568,7 +596,9 @@ class OuterSync:
             # one replica: the average of one is its own re-quantised slots. At n = 1 no bucket
             # is padded, so the buckets' slots are the tree's chunks in order and each kernel
             # covers the whole tree in one launch
-            self.k.delta_q8(self.tree, ALL, SLOT_INNER, self.theta, self.q_slots)
+            # (error feedback: only the encoder's residual -- re-quantising one peer's own
+            # slots is no second lossy stage to compensate)
+            self._delta_q8(ALL, self.q_slots)
             self.k.q8_reduce(self.q_slots, 1, self.tree.n_chunks, 1, self.q_slots)
             self.k.unpack_sgd_q8(self.tree, ALL, self.q_slots, self.theta, self.mom, self.lr,
                                  self.momentum, self.nesterov, self.steps_done == 0, SLOT_INNER)

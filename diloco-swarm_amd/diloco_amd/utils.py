@@ -54,7 +54,10 @@ For "device" and "host"/"lazy": fused (`get_outer_model(..., fused=)`, DILOCO_OU
 if unset) runs the four calls as one HBM pass at one peer (dl_delta_pack_sgd) and as
 pack -> exchange -> one SGD pass at N > 1, with .grad completing the deferred work when read
 and sync_inner_model a verified no-op after the step; wire (DILOCO_OUTER_WIRE, "f32";
-"bf16": BASELINE config #5's codec on the DP exchange); exchange (DILOCO_OUTER_EXCHANGE;
+"bf16": BASELINE config #5's codec on the DP exchange; "int8": one scale per 4096-element
+chunk, and with error_feedback (DILOCO_OUTER_Q8_EF, off if unset) both of its quantisers
+carry what they round away into the next outer step: dl_delta_q8_ef, dl_q8_reduce_ef;
+q8_error_feedback_state / load_q8_error_feedback_state); exchange (DILOCO_OUTER_EXCHANGE;
 "replicated", the host placement's default: all_reduce -> the SGD pass on every rank, so
 .grad and the momentum are local on every rank as in the reference; "sharded", the device
 placement's default: reduce_scatter -> SGD on this rank's 1/n -> all_gather of θ, SURVEY §8e;
@@ -89,6 +92,7 @@ _FUSED = "_diloco_fused"
 _WIRE = "_diloco_wire"
 _EXCHANGE = "_diloco_exchange"
 _EXCHANGE_ASKED = "_diloco_exchange_asked"  # by argument or DILOCO_OUTER_EXCHANGE
+_Q8_EF = "_diloco_q8_ef"  # int8 wire with error feedback (DILOCO_OUTER_Q8_EF)
 _ADAMW = "_diloco_adamw"  # an optim.OuterAdamW is attached
 OUTER_ADAMW = ("torch", "fused")
 INNER_ADAMW = ("torch", "fused")  # DILOCO_INNER_ADAMW: the inner optimizer's step
@@ -149,6 +153,8 @@ def outer_mirror(outer_model: nn.Module, device=None):
     m = getattr(outer_model, _ATTR, None)
     if m is None:
         k = default_kernels()
+        # the int8 wire's error feedback is named only where it is on (off: the call as before)
+        ef = {"error_feedback": True} if getattr(outer_model, _Q8_EF, False) else {}
         if getattr(outer_model, _PLACEMENT, "host") == "device":
             p = next(outer_model.parameters(), None)
             if p is None:
@@ -169,7 +175,7 @@ def outer_mirror(outer_model: nn.Module, device=None):
                                   wire=getattr(outer_model, _WIRE, "f32"),
                                   exchange=getattr(outer_model, _EXCHANGE,
                                                    DEFAULT_EXCHANGE["device"]),
-                                  keep_params=keep)
+                                  keep_params=keep, **ef)
             object.__setattr__(outer_model, _ATTR, m)
             _apply_adamw_mark(outer_model, m)
             return m
@@ -187,7 +193,7 @@ def outer_mirror(outer_model: nn.Module, device=None):
                                     fused=getattr(outer_model, _FUSED, True),
                                     wire=getattr(outer_model, _WIRE, "f32"),
                                     exchange=getattr(outer_model, _EXCHANGE,
-                                                     DEFAULT_EXCHANGE["host"]))
+                                                     DEFAULT_EXCHANGE["host"]), **ef)
         else:
             m = HostOuterMirror(outer_model, torch.device(device), kernels=k, write_back=wb)
         object.__setattr__(outer_model, _ATTR, m)  # not a submodule / not in state_dict
@@ -204,7 +210,7 @@ def _inner_device(inner_model: nn.Module) -> torch.device:
 
 def get_outer_model(inner_model: nn.Module, placement: str = None,
                     write_back: str = None, fused: bool = None, wire: str = None,
-                    exchange: str = None) -> nn.Module:
+                    exchange: str = None, error_feedback: bool = None) -> nn.Module:
     """Initializes the outer model from the inner model (src/utils.py:213-216).
 
     placement "host" (the reference's, default) or "device" (in HBM: on the inner model's GPU;
@@ -214,7 +220,10 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     (default on), wire ("f32" default, "bf16": BASELINE config #5's codec; "int8") and
     exchange ("replicated" for the host placement and "sharded" for placement="device" by
     default, or "a2a") for placement="device" and for the lazy host write-back (see the module
-    docstring)."""
+    docstring). error_feedback (int8 wire only; None reads DILOCO_OUTER_Q8_EF, default off):
+    both quantisers of the int8 exchange carry what they round away into the next outer step
+    (dl_delta_q8_ef, dl_q8_reduce_ef); q8_error_feedback_state / load_q8_error_feedback_state
+    let a checkpoint carry the residuals."""
     if placement is None:
         placement = os.environ.get("DILOCO_OUTER_PLACEMENT", "host")
     if placement not in PLACEMENTS:
@@ -229,6 +238,11 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
         wire = os.environ.get("DILOCO_OUTER_WIRE", "f32")
     if wire not in OUTER_WIRES:
         raise ValueError(f"wire {wire!r}: one of {OUTER_WIRES}")
+    if error_feedback is None:  # the variable is consulted for the int8 wire only
+        error_feedback = wire == "int8" and env_flag("DILOCO_OUTER_Q8_EF", False)
+    elif error_feedback and wire != "int8":
+        raise ValueError(f"error_feedback=True compensates the int8 wire's quantiser; the wire "
+                         f"is {wire!r}")
     if exchange is None:
         exchange = os.environ.get("DILOCO_OUTER_EXCHANGE") or None
     asked = exchange is not None
@@ -262,6 +276,7 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     object.__setattr__(outer_model, _WRITE_BACK, write_back)
     object.__setattr__(outer_model, _FUSED, bool(fused) and lazy)
     object.__setattr__(outer_model, _WIRE, wire)
+    object.__setattr__(outer_model, _Q8_EF, bool(error_feedback))
     object.__setattr__(outer_model, _EXCHANGE, exchange)
     object.__setattr__(outer_model, _EXCHANGE_ASKED, asked)
     if placement == "device" and has_params and not getattr(outer_model, _PENDING, False):
@@ -278,6 +293,35 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
         outer_model.register_state_dict_pre_hook(lambda mod, prefix, keep_vars:
                                                   flush_outer_model(mod))
     return outer_model
+
+
+def _q8_ef_mirror(outer_model: nn.Module):
+    m = getattr(outer_model, _ATTR, None)
+    return getattr(m, "dev", m)  # the lazy host placement steps on its HBM twin's mirror
+
+
+def q8_error_feedback_state(outer_model: nn.Module):
+    """The int8 wire's error-feedback residuals of this rank, for a checkpoint:
+    {"encode": the encoder's residual (packed layout), "reduce": [the residual of this rank's
+    re-quantised slots, per bucket]} as clones. None when the feature is off or no exchange has
+    run yet. The residuals are per rank (they are what this rank has not sent yet)."""
+    m = _q8_ef_mirror(outer_model)
+    if m is None or not getattr(m, "error_feedback", False):
+        return None
+    return m.q8_ef_state()
+
+
+def load_q8_error_feedback_state(outer_model: nn.Module, state) -> None:
+    """Copy a q8_error_feedback_state() back into an outer model built with the same tree,
+    buckets and peer count (ValueError otherwise). None resets every residual to zero -- also
+    the way out after a NaN/Inf pseudo-gradient left a non-finite residual."""
+    m = _q8_ef_mirror(outer_model)
+    if m is None or not getattr(m, "error_feedback", False):
+        if state is None:
+            return
+        raise ValueError("this outer model has no int8 error feedback to load a state into "
+                         "(the feature is off, or its device mirror is not built yet)")
+    m.load_q8_ef_state(state)
 
 
 def flush_outer_model(outer_model: nn.Module) -> None:

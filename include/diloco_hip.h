@@ -30,7 +30,7 @@ extern "C" {
 
 #define DL_API __attribute__((visibility("default")))
 
-#define DL_ABI_VERSION 7
+#define DL_ABI_VERSION 8
 #define DL_ALIGN_ELEMS 64      /* segment start alignment in the packed space: 256 B of fp32 */
 #define DL_CHUNK_ELEMS 4096    /* work unit of every segment walker: 16 KiB of fp32 */
 #define DL_ALL_BUCKETS (-1)
@@ -369,6 +369,35 @@ DL_API int dl_delta_q8(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
                        const float* outer_packed, void* slots, dl_stream_t stream);
 DL_API int dl_q8_reduce(const void* recv, int32_t n_peers, int32_t n_slots, int32_t divisor,
                         void* out, dl_stream_t stream);
+/* Error feedback for the two lossy stages (off unless the caller uses these entry points): what
+ * rounding removed is kept in an fp32 residual and added to the next outer step's value, so an
+ * element that stays below s/2 of its chunk is transmitted late instead of never. Each fp32
+ * operation rounds on its own.
+ * dl_delta_q8_ef, per chunk c of the bucket and element k of the packed space:
+ *   d = outer[k] - inner[seg][j]          (as dl_delta_q8)
+ *   x = d + r[k]                          (r = residual_packed: fp32, the tree's packed layout)
+ *   s = amax_chunk(|x|) / 127             (fmaxf: a NaN is ignored by the scale)
+ *   q = s == 0 ? 0 : clamp(rint(x / s), -127, 127)
+ *   slot(c) <- header(s), int8 q          (byte for byte what dl_delta_q8 writes for this x)
+ *   r[k] <- x - (float(q) * s)            (the product dl_unpack_*_q8 decode, then one subtract)
+ * r is read and written in place; nothing is loaded or stored past a chunk's length (the
+ * residual's padding is never written, the slot's bytes past the length stay zero). Results do
+ * not depend on the inner tensors' alignment, the grid or the bucket split. Non-finite values
+ * get no special case: a NaN/Inf element of d leaves a NaN (or Inf) residual, by IEEE rules,
+ * until the caller resets the residual to zero. slots, outer_packed and residual_packed
+ * non-null and 16-B aligned; the slot bound. 17.02 B/param: 12 read, 1.016 + 4 written.
+ * dl_q8_reduce_ef, on the owner of the n_slots slots:
+ *   acc = sum_r deq(recv[r][j]) in rank order; if divisor > 1: acc /= divisor (as dl_q8_reduce)
+ *   x = acc + r2[j*DL_CHUNK_ELEMS + i]; s, q as above over all DL_CHUNK_ELEMS values;
+ *   out slot j <- (s, q);  r2[...] <- x - float(q) * s
+ * residual: fp32, n_slots * DL_CHUNK_ELEMS elements, 16-B aligned. A zero padding slot and the
+ * zero tail of a short chunk give x = q = r2 = 0 and stay zero. out may alias recv only at
+ * n_peers == 1. Every peer still receives byte-identical averaged slots. */
+DL_API int dl_delta_q8_ef(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
+                          const float* outer_packed, float* residual_packed, void* slots,
+                          dl_stream_t stream);
+DL_API int dl_q8_reduce_ef(const void* recv, int32_t n_peers, int32_t n_slots, int32_t divisor,
+                           float* residual, void* out, dl_stream_t stream);
 DL_API int dl_unpack_sgd_q8(dl_tree_t tree, int32_t bucket, const void* slots,
                             float* outer_packed, float* mom_packed, float lr, float momentum,
                             int32_t nesterov, int32_t first_step, int32_t inner_slot,
