@@ -357,8 +357,12 @@ DL_API int dl_shard_reduce_adamw(const void* slices, int32_t wire_dtype, int32_t
 
 /* ---- int8 wire codec (not in the reference) --------------------------
  * One DL_Q8_SLOT_BYTES slot per chunk of the bucket, in chunk order: fp32 scale at byte 0,
- * zeros to byte 64 (the encoder and the reduce write the whole header), int8 values at byte
- * 64 (bytes past the chunk's length stay zero; slots must be zeroed once).
+ * zeros to byte 64, int8 values at byte 64, zeros past the chunk's length. The encoders
+ * (dl_delta_q8, dl_delta_q8_ef) and the reduces write every byte of each slot they are launched
+ * on -- the whole 64-B header and all DL_CHUNK_ELEMS payload bytes, zeros past the chunk's
+ * length -- whatever the slot held before, and no byte of any other slot. Only the slots no
+ * chunk owns (the zero slots that pad a bucket to a multiple of the peer count) are never
+ * written: the caller zeroes those once.
  * Quantiser: s = amax/127, q = s == 0 ? 0 : clamp(rint(x/s), -127, 127), value q*s.
  * dl_delta_q8:      slots <- quantise(outer - inner) per chunk  (a2, 8 B read + 1.02 B written)
  * dl_q8_reduce:     out[j] <- quantise((sum_r deq(recv[r][j])) / divisor), r in rank order;
@@ -380,9 +384,10 @@ DL_API int dl_q8_reduce(const void* recv, int32_t n_peers, int32_t n_slots, int3
  *   q = s == 0 ? 0 : clamp(rint(x / s), -127, 127)
  *   slot(c) <- header(s), int8 q          (byte for byte what dl_delta_q8 writes for this x)
  *   r[k] <- x - (float(q) * s)            (the product dl_unpack_*_q8 decode, then one subtract)
- * r is read and written in place; nothing is loaded or stored past a chunk's length (the
- * residual's padding is never written, the slot's bytes past the length stay zero). Results do
- * not depend on the inner tensors' alignment, the grid or the bucket split. Non-finite values
+ * r is read and written in place; of θ, inner and r nothing is loaded or stored past a chunk's
+ * length (the residual's padding is never written); the slot is written whole, as by
+ * dl_delta_q8, zeros past the length. Results do not depend on the inner tensors' alignment,
+ * the grid or the bucket split. Non-finite values
  * get no special case: a NaN/Inf element of d leaves a NaN (or Inf) residual, by IEEE rules,
  * until the caller resets the residual to zero. slots, outer_packed and residual_packed
  * non-null and 16-B aligned; the slot bound. 17.02 B/param: 12 read, 1.016 + 4 written.

@@ -56,7 +56,8 @@ def _inner_tensors(host, misaligned):
 
 
 class _Packed:
-    """θ, exp_avg, exp_avg_sq and a wire in a PackedTree's layout, with per-tensor access."""
+    """θ, exp_avg, exp_avg_sq and a wire in a PackedTree's layout, with per-tensor access.
+    Its padding checks use zero as the sentinel; tests/test_footprint_gpu.py pins the footprint."""
 
     def __init__(self, wire_dtype):
         self.tree = PackedTree(RAGGED, CAP)

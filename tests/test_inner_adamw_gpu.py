@@ -95,7 +95,8 @@ def _tensors(host, misaligned):
 
 
 class _State:
-    """A tree over `numels` with θ and g bound per tensor and zero exp_avg / exp_avg_sq arenas."""
+    """A tree over `numels` with θ and g bound per tensor and zero exp_avg / exp_avg_sq arenas.
+    Its padding checks use zero as the sentinel; tests/test_footprint_gpu.py pins the footprint."""
 
     def __init__(self, theta, th_mis=False, g_mis=False, numels=RAGGED, cap=CAP):
         self.numels = list(numels)

@@ -61,7 +61,8 @@ def _inner_tensors(host, misaligned):
 
 class _Packed:
     """θ, exp_avg, exp_avg_sq, an fp32 wire and the tree's int8 slots (one per chunk, in chunk
-    order, no padding slots) in a PackedTree's layout."""
+    order, no padding slots) in a PackedTree's layout.
+    Its padding checks use zero as the sentinel; tests/test_footprint_gpu.py pins the footprint."""
 
     def __init__(self, theta, inner0=None, misaligned=False):
         self.tree = PackedTree(RAGGED, CAP)

@@ -54,7 +54,8 @@ def _pseudo_gradient_tree(rng):
 
 class _Rig:
     """One tree on the device (θ, residual, slots, inner tensors) and its host twin on the
-    checker backend, fed the same values."""
+    checker backend, fed the same values.
+    Only the residual's padding holds a sentinel here; tests/test_footprint_gpu.py pins the footprint."""
 
     def __init__(self, misaligned=False, max_blocks=0):
         self.tree = PackedTree(NUMELS, CAP)
