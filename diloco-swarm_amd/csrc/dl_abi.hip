@@ -1069,6 +1069,46 @@ DL_API int dl_unpack_avg_sumsq(dl_tree_t t, int32_t b, const void* wire, int32_t
                          : hip_fail(e, "dl_unpack_avg_sumsq");
 }
 
+// The gradient side of the int8 exchange (dl_q8_grad.hip). The encoders take dl_delta_q8's
+// policy, the decoder dl_unpack_avg's. The buffer checks need no tree and come first, so every
+// argument error is reported before any device call.
+DL_API int dl_gather_q8(dl_tree_t t, int32_t b, int32_t src_slot, void* slots, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_packed(slots, "dl_gather_q8", "slots"));
+  DL_TRY(make_launch(t, b, s, &L, "dl_gather_q8", kAutoDeltaQ8));
+  DL_TRY(check_slot(t, src_slot, "dl_gather_q8"));
+  DL_TRY(slot_begin(t, src_slot, L.stream, "dl_gather_q8"));
+  hipError_t e = dl::launch_gather_q8(L, src_slot, nullptr, static_cast<uint8_t*>(slots));
+  return e == hipSuccess ? slot_end(t, src_slot, L.stream, "dl_gather_q8")
+                         : hip_fail(e, "dl_gather_q8");
+}
+
+DL_API int dl_gather_q8_ef(dl_tree_t t, int32_t b, int32_t src_slot, float* residual, void* slots,
+                           dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_packed(residual, "dl_gather_q8_ef", "residual"));
+  DL_TRY(check_packed(slots, "dl_gather_q8_ef", "slots"));
+  DL_TRY(make_launch(t, b, s, &L, "dl_gather_q8_ef", kAutoDeltaQ8));
+  DL_TRY(check_slot(t, src_slot, "dl_gather_q8_ef"));
+  DL_TRY(slot_begin(t, src_slot, L.stream, "dl_gather_q8_ef"));
+  hipError_t e = dl::launch_gather_q8(L, src_slot, residual, static_cast<uint8_t*>(slots));
+  return e == hipSuccess ? slot_end(t, src_slot, L.stream, "dl_gather_q8_ef")
+                         : hip_fail(e, "dl_gather_q8_ef");
+}
+
+DL_API int dl_unpack_avg_q8(dl_tree_t t, int32_t b, const void* slots, int32_t dst_slot,
+                            double* partials, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_packed(slots, "dl_unpack_avg_q8", "slots"));
+  if (partials) DL_TRY(check_partials(partials, "dl_unpack_avg_q8"));
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_avg_q8", kAutoNT, Big::two_chunks));
+  DL_TRY(check_slot(t, dst_slot, "dl_unpack_avg_q8"));
+  DL_TRY(slot_begin(t, dst_slot, L.stream, "dl_unpack_avg_q8"));
+  hipError_t e = dl::launch_unpack_avg_q8(L, static_cast<const uint8_t*>(slots), dst_slot, partials);
+  return e == hipSuccess ? slot_end(t, dst_slot, L.stream, "dl_unpack_avg_q8")
+                         : hip_fail(e, "dl_unpack_avg_q8");
+}
+
 DL_API int dl_norm_finish(const double* partials, int32_t n_partials, float max_norm, float* out2,
                           dl_stream_t s) {
   if (n_partials < 0) return fail(DL_E_ARG, "dl_norm_finish: n_partials %d", n_partials);

@@ -99,6 +99,12 @@ hipError_t launch_unpack_sgd_q8(const Launch& L, const uint8_t* slots, float* ou
                                 SgdArgs a, int inner_slot);
 hipError_t launch_unpack_adamw_q8(const Launch& L, const uint8_t* slots, float* outer, float* m1,
                                   float* m2, AdamArgs a, int inner_slot);
+// the gradient side of the int8 exchange (dl_q8_grad.hip). resid: the encoder's packed residual
+// (dl_gather_q8_ef), or nullptr (dl_gather_q8); partials: per-chunk Σ g² of the values stored,
+// or nullptr for none
+hipError_t launch_gather_q8(const Launch& L, int src_slot, float* resid, uint8_t* slots);
+hipError_t launch_unpack_avg_q8(const Launch& L, const uint8_t* slots, int dst_slot,
+                                double* partials);
 // resid: the owner's stage-2 residual (dl_q8_reduce_ef), or nullptr (dl_q8_reduce)
 hipError_t launch_q8_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,
                             float* resid, uint8_t* out, hipStream_t s);

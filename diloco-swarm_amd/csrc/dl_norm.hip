@@ -24,28 +24,10 @@
 // |g| >~ 1.8e19; the fp64 sum does not (1e25 has a finite norm here).
 // No MFMA, no scratch; 32 B of LDS (profiles/clip_norm_resource_usage.txt).
 #include "dl_device.h"
+#include "dl_norm_dev.h"
 
 namespace dl {
 namespace {
-
-__device__ __forceinline__ void sq1(double& acc, float g) { acc += double(g) * double(g); }
-__device__ __forceinline__ void sq4(double& acc, const float4& x) {
-  sq1(acc, x.x);
-  sq1(acc, x.y);
-  sq1(acc, x.z);
-  sq1(acc, x.w);
-}
-
-// Σ over the workgroup's 256 lanes in the fixed order above; the result is valid in lane 0
-__device__ __forceinline__ double block_sum(double v, int tid) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);  // 64-lane wave
-  __shared__ double part[kThreads / 64];
-  if ((tid & 63) == 0) part[tid >> 6] = v;
-  __syncthreads();
-  if (tid == 0) v = ((part[0] + part[1]) + part[2]) + part[3];
-  __syncthreads();  // `part` is reused by the workgroup's next chunk
-  return v;
-}
 
 // the float4 rows of a chunk a lane owns, from a tensor that may be only 4-B aligned
 template <bool NTL>
@@ -63,16 +45,6 @@ __device__ __forceinline__ void load_rows(const float* src, int nv, int tid, flo
       if (v < nv) x[u] = make_float4(src[4 * v], src[4 * v + 1], src[4 * v + 2], src[4 * v + 3]);
     }
   }
-}
-
-__device__ __forceinline__ double sumsq_rows(const float4 (&x)[kUnroll], int nv, int tid) {
-  double acc = 0.0;
-#pragma unroll
-  for (int u = 0; u < kUnroll; ++u) {
-    const int v = u * kThreads + tid;
-    if (v < nv) sq4(acc, x[u]);
-  }
-  return acc;
 }
 
 struct SumSq {

@@ -153,6 +153,20 @@ def dp_backend() -> str:
 # rank-order average + all_gather (deterministic, bit-exact vs the oracle at any n) for the
 # device gradients AND for the outer model's mirror (both placements)
 DP_EXCHANGE = os.environ.get("DILOCO_DP_EXCHANGE", "rccl")
+# The wire of the device-gradient GradSync (only that branch: the outer model's mirror has its
+# own, DILOCO_OUTER_WIRE, and the host loop none): "f32", "bf16", or "int8" -- the outer step's
+# int8 codec on the per-step exchange, 2(n-1)/n * 1.016 bus bytes per parameter against
+# 8(n-1)/n, with DP_Q8_EF (consulted for int8 only, off if unset) both quantisers' error feedback
+DP_WIRES = {"f32": torch.float32, "bf16": torch.bfloat16, "int8": torch.int8}
+DP_WIRE = os.environ.get("DILOCO_DP_WIRE", "f32")
+DP_Q8_EF = os.environ.get("DILOCO_DP_Q8_EF", "0").strip().lower() in ("1", "true", "yes", "on")
+
+
+def dp_wire():
+    """(wire dtype, error feedback) of the GradSync that DPSync builds, from DP_WIRE / DP_Q8_EF."""
+    if DP_WIRE not in DP_WIRES:
+        raise ValueError(f"DILOCO_DP_WIRE {DP_WIRE!r}: one of {tuple(DP_WIRES)}")
+    return DP_WIRES[DP_WIRE], DP_WIRE == "int8" and bool(DP_Q8_EF)
 
 
 class DPSync:
@@ -226,8 +240,9 @@ class DPSync:
                 p.grad = torch.zeros_like(p)
         gs = self._grad_syncs.get(id(model))
         if gs is None or not gs.matches(params):
-            gs = GradSync(params, self.dp_group(params[0].device), num_peers,
-                          exchange=DP_EXCHANGE)
+            wire, ef = dp_wire()
+            gs = GradSync(params, self.dp_group(params[0].device), num_peers, wire_dtype=wire,
+                          exchange=DP_EXCHANGE, error_feedback=ef)
             self._grad_syncs[id(model)] = gs
         return gs.sync(max_norm)
 

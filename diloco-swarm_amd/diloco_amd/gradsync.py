@@ -16,10 +16,24 @@ of the averaged shards -> dl_unpack_avg (a copy): the same bus bytes as the all-
 average that does not depend on RCCL's algorithm and is bit-exact against oracle/or_sum_avg at
 every n.
 
+wire_dtype=torch.int8: the int8 wire of the outer step (dl_q8.hip; one DL_Q8_SLOT_BYTES slot
+per chunk, bucket b's slots padded with zero slots to a multiple of the peer count; plan.
+q8_slot_plan) on the exchange that runs every step -- per bucket dl_gather_q8 -> RCCL all_to_all
+of the slots -> dl_q8_reduce (Σ of the peers' dequantised slots in rank order, / n, re-quantised)
+-> RCCL all_gather -> dl_unpack_avg_q8 (q·s into .grad): 2(n-1)/n · 1.016 bus bytes per
+parameter against 8(n-1)/n, every peer left with byte-identical gradients. error_feedback=True:
+dl_gather_q8_ef and dl_q8_reduce_ef in their places -- what each quantiser rounds away is added
+to the next step's value (q_residual, 4 B/param; q_residual_red, 4/n B/param; both stay on
+this peer; q8_ef_state / load_q8_ef_state). One replica: encode, the plain in-place re-quantise,
+decode -- only the encoder's residual. A NaN/Inf gradient leaves a non-finite residual (IEEE
+rules, as in the outer codec) until load_q8_ef_state(None) resets it. The residuals belong to
+this GradSync: one rebuilt for other parameters starts from zero.
+
 sync(max_norm): the clip_grad_norm_ that follows the sync in the training loop
 (src/train.py:255), fused into it. Every dl_unpack_avg becomes dl_unpack_avg_sumsq, which holds
 each averaged gradient in registers on its way to .grad and leaves the chunk's Σ g²; after the
-last bucket dl_norm_finish and one dl_scale_by run on the same stream. Equal, bit for bit, to
+last bucket dl_norm_finish and one dl_scale_by run on the same stream (int8 wire:
+dl_unpack_avg_q8 leaves the same partial sums). Equal, bit for bit, to
 sync() followed by utils.clip_grad_norm_, without that call's read of every gradient.
 """
 from __future__ import annotations
@@ -29,17 +43,17 @@ from typing import Optional, Sequence
 import torch
 import torch.distributed as dist
 
-from .kernels import default_kernels
+from .kernels import Q8_SLOT, default_kernels
 from . import _lib
 from .outer import _Done, pipelined_buckets
-from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_GRAD
+from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_GRAD, q8_slot_plan
 
 
 class GradSync:
     def __init__(self, params: Sequence[torch.Tensor], group: Optional[dist.ProcessGroup],
                  world_size: int, wire_dtype: torch.dtype = torch.float32,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, kernels=None,
-                 exchange: str = "rccl"):
+                 exchange: str = "rccl", error_feedback: bool = False):
         self.params = list(params)
         self.k = kernels or default_kernels()
         self.device = self.params[0].device
@@ -47,6 +61,16 @@ class GradSync:
         if exchange not in ("rccl", "a2a"):
             raise ValueError(f"exchange {exchange!r}: 'rccl' or 'a2a'")
         self.a2a = exchange == "a2a"
+        self.q8 = wire_dtype == torch.int8
+        # int8 wire only: carry what each quantiser rounds away into the next sync
+        # (dl_gather_q8_ef, dl_q8_reduce_ef)
+        self.error_feedback = bool(error_feedback)
+        if self.error_feedback and not self.q8:
+            raise ValueError("error_feedback compensates the int8 wire's quantiser; it needs "
+                             "wire_dtype=torch.int8")
+        if self.q8 and self.a2a:
+            raise ValueError("the int8 wire has its own rank-order exchange; exchange='a2a' "
+                             "averages the fp32 grads")
         if dist.is_initialized() and self.world_size > 1:
             gs = dist.get_world_size(group)
             if gs != self.world_size:  # the collectives would reduce over the wrong ranks
@@ -63,7 +87,11 @@ class GradSync:
         # a2a: buckets split into n equal 64-element-aligned shards
         balign = _lib.ALIGN_ELEMS * (self.world_size if self.a2a else 1)
         self.tree = self.k.tree(self.numels, self.device, bucket_cap_elems, balign)
-        self.wire = torch.zeros(self.tree.total, dtype=wire_dtype, device=self.device)
+        if self.q8:
+            self.wire = None
+            self._alloc_q8()
+        else:
+            self.wire = torch.zeros(self.tree.total, dtype=wire_dtype, device=self.device)
         if self.a2a:
             n = self.world_size
             smax = max((hi - lo) // n for lo, hi in self.tree.bucket_ranges) if \
@@ -75,6 +103,65 @@ class GradSync:
         # own stream, joined back into the caller's (see OuterSync.stream)
         self.stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
         self.partials = None  # per-chunk Σ g² of sync(max_norm), created on first use
+
+    def _alloc_q8(self) -> None:
+        """OuterSync's slot plan: a region of n * m_b slots per bucket, zero at allocation (the
+        padding slots are never encoded), landing and reduce buffers for two buckets in flight."""
+        n = self.world_size
+        self.q8_plan, total, _owned, mmax = q8_slot_plan(self.tree.bucket_chunks, n)
+        z = dict(dtype=torch.uint8, device=self.device)
+        self.q_slots = torch.zeros(total * Q8_SLOT, **z)
+        self.q_recv = self.q_red = None
+        if not self.local:
+            self.q_recv = [torch.zeros(n * mmax * Q8_SLOT, **z) for _ in range(2)]
+            self.q_red = [torch.zeros(mmax * Q8_SLOT, **z) for _ in range(2)]
+        # error feedback: the encoder's residual in the packed layout, and at n > 1 the
+        # residual of this peer's m_b re-quantised slots of every bucket
+        self.q_residual = self.q_residual_red = None
+        if self.error_feedback:
+            f = dict(dtype=torch.float32, device=self.device)
+            self.q_residual = torch.zeros(self.tree.total, **f)
+            if n > 1:
+                self.q_residual_red = [torch.zeros(m * _lib.CHUNK_ELEMS, **f)
+                                       for _nch, m, _at, _rat in self.q8_plan]
+
+    def q8_region(self, bucket: int) -> torch.Tensor:
+        """The int8 slots of one bucket (n * m slots, chunk order, zero padding at the end)."""
+        _nch, m, at, _rat = self.q8_plan[bucket]
+        return self.q_slots[at * Q8_SLOT:(at + self.world_size * m) * Q8_SLOT]
+
+    def q8_ef_state(self) -> Optional[dict]:
+        """{"encode": the encoder's residual, "reduce": [this peer's stage-2 residual per
+        bucket]} as clones (the mirror's q8_ef_state); None when error feedback is off."""
+        if not self.error_feedback:
+            return None
+        return {"encode": self.q_residual.clone(),
+                "reduce": [r.clone() for r in self.q_residual_red or []]}
+
+    def load_q8_ef_state(self, state: Optional[dict]) -> None:
+        """Copy a q8_ef_state() back (None: reset every residual to zero). A state that does
+        not fit this exchange's buckets and peer count raises ValueError."""
+        if not self.error_feedback:
+            if state is None:
+                return
+            raise ValueError("this gradient sync runs without int8 error feedback")
+        dst = self.q_residual_red or []
+        if state is None:
+            self.q_residual.zero_()
+            for r in dst:
+                r.zero_()
+            return
+        enc, red = state["encode"], list(state["reduce"])
+        if tuple(enc.shape) != (self.tree.total,):
+            raise ValueError(f"int8 error-feedback state: encode residual of {tuple(enc.shape)}, "
+                             f"expected ({self.tree.total},)")
+        if len(red) != len(dst) or any(tuple(a.shape) != tuple(d.shape)
+                                       for a, d in zip(red, dst)):
+            raise ValueError("the int8 error-feedback state does not match this exchange's "
+                             "buckets and peer count")
+        self.q_residual.copy_(enc)
+        for d, a in zip(dst, red):
+            d.copy_(a)
 
     def matches(self, params: Sequence[torch.Tensor]) -> bool:
         return len(params) == len(self.params) and all(
@@ -130,6 +217,9 @@ class GradSync:
         # one replica (self.local): the all-reduce is the identity (the rebinding, gather and
         # /1 still run, so the path is exercised on a one-GPU machine)
         local = self.local
+        if self.q8:
+            self._sync_q8(clip)
+            return
         if self.a2a and not local:
             self._sync_a2a(clip)
             return
@@ -174,6 +264,61 @@ class GradSync:
                 self._unpack(b - 1, 1, clip)
         ag[nb - 1].wait()
         self._unpack(nb - 1, 1, clip)
+
+    def _sync_q8(self, clip=None) -> None:
+        """gather_q8(b) -> all_to_all(b) | q8_reduce(b) -> all_gather(b) | unpack_avg_q8(b),
+        overlapped across buckets like _sync_a2a; the landing and reduce buffers alternate, so
+        the bytes do not depend on the overlap."""
+        n, nb = self.world_size, self.tree.n_buckets
+        partials = None if clip is None else self.partials
+
+        def encode(b):
+            if self.error_feedback:
+                self.k.gather_q8_ef(self.tree, b, SLOT_GRAD, self.q_residual, self.q8_region(b))
+            else:
+                self.k.gather_q8(self.tree, b, SLOT_GRAD, self.q8_region(b))
+
+        def decode(b):
+            self.k.unpack_avg_q8(self.tree, b, self.q8_region(b), SLOT_GRAD, partials)
+
+        if self.local:
+            # one replica: the average of one is its own re-quantised slots (error feedback:
+            # only the encoder's residual -- re-quantising one peer's own slots is no second
+            # lossy stage to compensate), so a one-GPU machine exercises the path
+            for b in range(nb):
+                region = self.q8_region(b)
+                encode(b)
+                self.k.q8_reduce(region, 1, self.q8_plan[b][1], 1, region)
+                decode(b)
+            return
+
+        def a2a(b):
+            m = self.q8_plan[b][1]
+            encode(b)
+            return dist.all_to_all_single(self.q_recv[b % 2][:n * m * Q8_SLOT], self.q8_region(b),
+                                          group=self.group, async_op=True)
+
+        if nb == 0:
+            return
+        x, ag = [None] * nb, [None] * nb
+        x[0] = a2a(0)
+        for b in range(nb):
+            if b + 1 < nb:
+                x[b + 1] = a2a(b + 1)
+            x[b].wait()
+            m = self.q8_plan[b][1]
+            recv, red = self.q_recv[b % 2][:n * m * Q8_SLOT], self.q_red[b % 2][:m * Q8_SLOT]
+            if self.q_residual_red is not None:
+                self.k.q8_reduce_ef(recv, n, m, n, self.q_residual_red[b], red)
+            else:
+                self.k.q8_reduce(recv, n, m, n, red)
+            ag[b] = dist.all_gather_into_tensor(self.q8_region(b), red, group=self.group,
+                                                async_op=True)
+            if b >= 1:
+                ag[b - 1].wait()
+                decode(b - 1)
+        ag[nb - 1].wait()
+        decode(nb - 1)
 
     def close(self) -> None:
         self.tree.close()

@@ -240,6 +240,23 @@ class HipKernels:
                   exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars, int(inner_slot),
                   _s(theta))
 
+    # the gradient side of the int8 exchange (dl_q8_grad.hip)
+    def gather_q8(self, tree, bucket, src_slot, slots) -> None:
+        """slots <- quantise(the gradients bound to src_slot), one slot per chunk."""
+        _lib.call("dl_gather_q8", tree.handle, bucket, int(src_slot), slots.data_ptr(), _s(slots))
+
+    def gather_q8_ef(self, tree, bucket, src_slot, residual, slots) -> None:
+        """gather_q8 with error feedback: x = g + residual is quantised and
+        residual <- x - q·s in place (fp32, the tree's packed layout)."""
+        _lib.call("dl_gather_q8_ef", tree.handle, bucket, int(src_slot), residual.data_ptr(),
+                  slots.data_ptr(), _s(slots))
+
+    def unpack_avg_q8(self, tree, bucket, slots, dst_slot, partials=None) -> None:
+        """dst_slot <- q·s of the averaged slots; with partials also the per-chunk Σ of the
+        stored values² (grad_sumsq's, for norm_finish)."""
+        _lib.call("dl_unpack_avg_q8", tree.handle, bucket, slots.data_ptr(), int(dst_slot),
+                  _ptr(partials), _s(slots))
+
     def unpack_avg(self, tree, bucket, wire, divisor, dst_slot, dst_packed=None) -> None:
         _lib.call("dl_unpack_avg", tree.handle, bucket, wire.data_ptr(), wire_code(wire.dtype),
                   int(divisor), int(dst_slot), _ptr(dst_packed), _s(wire))

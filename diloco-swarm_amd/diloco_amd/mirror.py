@@ -41,7 +41,7 @@ import torch.distributed as dist
 from . import _lib
 from .kernels import default_kernels
 from .outer import pipelined_buckets
-from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_GRAD, SLOT_INNER
+from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_GRAD, SLOT_INNER, q8_slot_plan
 
 ALL = _lib.ALL_BUCKETS
 S_CHUNK = _lib.CHUNK_ELEMS  # elements per tree chunk (one int8 slot each)
@@ -1272,13 +1272,7 @@ class DeviceOuterMirror:
             return q
         from .kernels import Q8_SLOT
 
-        plan, base, rbase, mmax = [], 0, 0, 1
-        for c0, c1 in self.tree.bucket_chunks:
-            m = max(1, -(-(c1 - c0) // n))
-            plan.append((c1 - c0, m, base, rbase))
-            base += n * m
-            rbase += m
-            mmax = max(mmax, m)
+        plan, base, rbase, mmax = q8_slot_plan(self.tree.bucket_chunks, n)
         z = dict(dtype=torch.uint8, device=self.device)
         segs = []
         for lo, hi in self.tree.bucket_ranges:

@@ -43,7 +43,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .kernels import Q8_SLOT, default_kernels
-from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_INNER
+from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_INNER, q8_slot_plan
 
 ALL = _lib.ALL_BUCKETS
 # Tile of dl_pack_sgd_tiled: 8192 chunks = 32 Mi elements, 128 MiB per stream (wire + θ of a
@@ -206,12 +206,8 @@ class OuterSync:
             # int8 codec: one Q8_SLOT-byte slot per chunk; bucket b's slots padded to a
             # multiple of the peer count so both exchanges split evenly (dl_q8.hip)
             n = self.world_size
-            self.q8_plan, base, mmax = [], 0, 1
-            for c0, c1 in self.tree.bucket_chunks:
-                m = max(1, -(-(c1 - c0) // n))
-                self.q8_plan.append((c1 - c0, m, base))
-                base += n * m
-                mmax = max(mmax, m)
+            plan, base, _owned, mmax = q8_slot_plan(self.tree.bucket_chunks, n)
+            self.q8_plan = [(nch, m, at) for nch, m, at, _rat in plan]
             self.wire = None
             self.q_slots = torch.zeros(base * Q8_SLOT, dtype=torch.uint8, **z)
             self.q_recv = torch.zeros(n * mmax * Q8_SLOT, dtype=torch.uint8, **z)

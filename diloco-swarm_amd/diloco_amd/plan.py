@@ -44,6 +44,22 @@ def plan_tables(numels: Sequence[int], cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS
     return seg, bnd[: nb.value + 1].copy()
 
 
+def q8_slot_plan(bucket_chunks: Sequence[Tuple[int, int]], n_peers: int):
+    """Slot plan of the int8 exchange (dl_q8.hip): bucket b gets a region of n_peers * m_b
+    slots with m_b = max(1, ceil(chunks_b / n_peers)), so the all_to_all and the all_gather
+    split evenly; the slots no chunk owns stay zero. Returns (plan, slots, owned, m_max):
+    plan[b] = (chunks_b, m_b, first slot of the region, first of this peer's m_b reduced slots
+    among all buckets'), the slots of all regions, Σ m_b, and max m_b (at least 1)."""
+    plan, base, rbase, mmax = [], 0, 0, 1
+    for c0, c1 in bucket_chunks:
+        m = max(1, -(-(c1 - c0) // n_peers))
+        plan.append((c1 - c0, m, base, rbase))
+        base += n_peers * m
+        rbase += m
+        mmax = max(mmax, m)
+    return plan, base, rbase, mmax
+
+
 class PackedTree:
     """Device handle (dl_tree_t) for one parameter tree on the current HIP device."""
 

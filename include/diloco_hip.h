@@ -104,7 +104,8 @@ DL_API int dl_tree_bind(dl_tree_t tree, int32_t slot, const uint64_t* dev_ptrs, 
 /* Launch shape of every walker kernel on this tree: max_blocks caps the grid (0 = one
  * workgroup per chunk, the default); flags = DL_TUNE_AUTO (the default: the measured
  * per-kernel choice -- NT loads everywhere; NT stores in the SGD kernels, dl_scatter,
- * dl_unpack_avg, dl_unpack_sgd_q8 and dl_unpack_adamw_q8, and in dl_delta_pack / dl_gather over launches of more
+ * dl_unpack_avg, dl_unpack_sgd_q8, dl_unpack_adamw_q8, dl_unpack_avg_q8 and the int8 encoders
+ * (dl_delta_q8, dl_gather_q8 and their _ef forms), and in dl_delta_pack / dl_gather over launches of more
  * than 2^28 elements; plain stores for those two producers below that size, where the next
  * kernel or RCCL re-reads their output from the Infinity Cache) or DL_TUNE_NT_LOADS [|
  * DL_TUNE_NT_STORES] for every kernel. Plain loads, DL_TUNE_WT_STORES (write-through, sc1)
@@ -425,6 +426,37 @@ DL_API int dl_unpack_adamw_q8(dl_tree_t tree, int32_t bucket, const void* slots,
                               float* exp_avg_sq_packed, float decay, float w1, float beta2,
                               float w2, float neg_step_size, float bc2_sqrt, float eps,
                               int32_t inner_slot, dl_stream_t stream);
+/* The gradient side of the int8 exchange: the per-step DP average of device gradients
+ * (src/train.py:249-251) over the same slots, reduces (dl_q8_reduce, dl_q8_reduce_ef with
+ * divisor n_peers) and collectives as the pseudo-gradient's. Slot of chunk c at (c - first
+ * chunk of the bucket) * DL_Q8_SLOT_BYTES; the whole tree with DL_ALL_BUCKETS.
+ * dl_gather_q8, per chunk c of the bucket, g = slot src_slot (per-tensor fp32):
+ *   slot(c) <- header(s), int8 q of x = g[seg][j]     (s, q: the quantiser above)
+ * byte for byte what dl_delta_q8 writes for outer = g, inner = +0 (x - (+0) = x bit for bit).
+ * 5.02 B/param: 4 read, 1.016 written.
+ * dl_gather_q8_ef, with the encoder's residual r = residual_packed (fp32, the packed layout):
+ *   x = g[seg][j] + r[k];  slot(c) <- header(s), int8 q of x;  r[k] <- x - (float(q) * s)
+ * dl_delta_q8_ef with d replaced by g; r is read and written in place by the same lane.
+ * 13.02 B/param: 8 read, 1.016 + 4 written.
+ * Both write every byte of each slot of the bucket -- the 64-B header whole, zeros past the
+ * chunk's length -- whatever the slot held before, and no byte of any other slot; of g and r
+ * nothing is loaded or stored past a chunk's length (the residual's padding is never written).
+ * Results do not depend on the gradient tensors' alignment, the grid or the bucket split. A
+ * NaN/Inf gradient leaves a NaN/Inf residual, by IEEE rules, until the caller resets it.
+ * dl_unpack_avg_q8, per chunk c of the bucket, dst = slot dst_slot (per-tensor fp32):
+ *   dst[seg][j] = float(int8 q) * s       (one rounded fp32 multiply: the product
+ *                                          dl_unpack_sgd_q8 decodes)
+ *   partials[c] = Σ over the values stored to chunk c, when partials is not NULL: fp64, in
+ *                 dl_grad_sumsq's order, bit-identical to dl_grad_sumsq on dst afterwards;
+ *                 written for exactly the bucket's chunk range (n_chunk doubles, 8-B aligned)
+ * The slots are only read; nothing is stored past a tensor's length. 5.02 B/param: 1.016 read,
+ * 4 written. slots and residual_packed non-null and 16-B aligned; the slot bound. */
+DL_API int dl_gather_q8(dl_tree_t tree, int32_t bucket, int32_t src_slot, void* slots,
+                        dl_stream_t stream);
+DL_API int dl_gather_q8_ef(dl_tree_t tree, int32_t bucket, int32_t src_slot,
+                           float* residual_packed, void* slots, dl_stream_t stream);
+DL_API int dl_unpack_avg_q8(dl_tree_t tree, int32_t bucket, const void* slots, int32_t dst_slot,
+                            double* partials, dl_stream_t stream);
 
 /* ---- serializer (src/serializer.py:11-15) ----------------------------------------------
  * out is fp32 of 2*numel elements: out[0] = meta0, out[1] = meta1, out[numel + i] =
