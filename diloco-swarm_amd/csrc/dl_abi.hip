@@ -999,6 +999,71 @@ DL_API int dl_unpack_adamw_q8(dl_tree_t t, int32_t b, const void* slots, float* 
                          : hip_fail(e, "dl_unpack_adamw_q8");
 }
 
+// The fp4 wire (dl_fp4.hip): the launches and store policies of the int8 calls they stand in
+// for; a null residual selects the kernels without error feedback.
+DL_API int dl_delta_fp4(dl_tree_t t, int32_t b, int32_t inner_slot, const float* outer,
+                        float* residual, void* slots, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_delta_fp4", kAutoDeltaQ8));
+  DL_TRY(check_slot(t, inner_slot, "dl_delta_fp4"));
+  DL_TRY(check_packed(outer, "dl_delta_fp4", "outer"));
+  if (residual) DL_TRY(check_packed(residual, "dl_delta_fp4", "residual"));
+  DL_TRY(check_packed(slots, "dl_delta_fp4", "slots"));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_delta_fp4"));
+  hipError_t e = dl::launch_delta_fp4(L, inner_slot, outer, residual, static_cast<uint8_t*>(slots));
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_fp4")
+                         : hip_fail(e, "dl_delta_fp4");
+}
+
+DL_API int dl_fp4_reduce(const void* recv, int32_t n, int32_t m, int32_t divisor, float* residual,
+                         void* out, dl_stream_t s) {
+  if (n < 1 || m < 0 || divisor < 1)
+    return fail(DL_E_ARG, "dl_fp4_reduce: n %d m %d div %d", n, m, divisor);
+  DL_TRY(check_packed(recv, "dl_fp4_reduce", "recv"));
+  if (residual) DL_TRY(check_packed(residual, "dl_fp4_reduce", "residual"));
+  DL_TRY(check_packed(out, "dl_fp4_reduce", "out"));
+  if (recv == out && n != 1) return fail(DL_E_ARG, "dl_fp4_reduce: in place needs n_peers == 1");
+  hipError_t e = dl::launch_fp4_reduce(static_cast<const uint8_t*>(recv), n, m, divisor, residual,
+                                       static_cast<uint8_t*>(out), static_cast<hipStream_t>(s));
+  return e == hipSuccess ? DL_OK : hip_fail(e, "dl_fp4_reduce");
+}
+
+DL_API int dl_unpack_sgd_fp4(dl_tree_t t, int32_t b, const void* slots, float* outer, float* mom,
+                             float lr, float momentum, int32_t nesterov, int32_t first_step,
+                             int32_t inner_slot, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_sgd_fp4", kAutoNT));
+  DL_TRY(check_packed(slots, "dl_unpack_sgd_fp4", "slots"));
+  DL_TRY(check_packed(outer, "dl_unpack_sgd_fp4", "outer"));
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_unpack_sgd_fp4", mom, lr, momentum, nesterov, first_step, &a));
+  DL_TRY(check_slot(t, inner_slot, "dl_unpack_sgd_fp4", true));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_sgd_fp4"));
+  hipError_t e = dl::launch_unpack_sgd_fp4(L, static_cast<const uint8_t*>(slots), outer, mom, a,
+                                           inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_sgd_fp4")
+                         : hip_fail(e, "dl_unpack_sgd_fp4");
+}
+
+DL_API int dl_unpack_adamw_fp4(dl_tree_t t, int32_t b, const void* slots, float* outer,
+                               float* exp_avg, float* exp_avg_sq, float decay, float w1,
+                               float beta2, float w2, float neg_step_size, float bc2_sqrt,
+                               float eps, int32_t inner_slot, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_adamw_fp4", kAutoNT));
+  DL_TRY(check_packed(slots, "dl_unpack_adamw_fp4", "slots"));
+  DL_TRY(check_packed(outer, "dl_unpack_adamw_fp4", "outer"));
+  DL_TRY(check_packed(exp_avg, "dl_unpack_adamw_fp4", "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, "dl_unpack_adamw_fp4", "exp_avg_sq"));
+  DL_TRY(check_slot(t, inner_slot, "dl_unpack_adamw_fp4", true));
+  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_adamw_fp4"));
+  hipError_t e = dl::launch_unpack_adamw_fp4(L, static_cast<const uint8_t*>(slots), outer, exp_avg,
+                                             exp_avg_sq, a, inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_adamw_fp4")
+                         : hip_fail(e, "dl_unpack_adamw_fp4");
+}
+
 DL_API int dl_gather(dl_tree_t t, int32_t b, int32_t src_slot, void* packed, int32_t dtype,
                      dl_stream_t s) {
   dl::Launch L;

@@ -108,6 +108,16 @@ hipError_t launch_unpack_avg_q8(const Launch& L, const uint8_t* slots, int dst_s
 // resid: the owner's stage-2 residual (dl_q8_reduce_ef), or nullptr (dl_q8_reduce)
 hipError_t launch_q8_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,
                             float* resid, uint8_t* out, hipStream_t s);
+// the fp4 (MXFP4) wire of the pseudo-gradient exchange (dl_fp4.hip). resid: the encoder's packed
+// residual / the owner's stage-2 residual, or nullptr for no error feedback
+hipError_t launch_delta_fp4(const Launch& L, int inner_slot, const float* outer, float* resid,
+                            uint8_t* slots);
+hipError_t launch_fp4_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,
+                             float* resid, uint8_t* out, hipStream_t s);
+hipError_t launch_unpack_sgd_fp4(const Launch& L, const uint8_t* slots, float* outer, float* mom,
+                                 SgdArgs a, int inner_slot);
+hipError_t launch_unpack_adamw_fp4(const Launch& L, const uint8_t* slots, float* outer, float* m1,
+                                   float* m2, AdamArgs a, int inner_slot);
 hipError_t launch_unpack_adamw(const Launch& L, const void* wire, int wire_dtype, int divisor,
                                float* outer, float* m1, float* m2, AdamArgs a, int inner_slot);
 hipError_t launch_delta_pack_adamw(const Launch& L, int inner_slot, float* outer, void* wire,

@@ -21,6 +21,7 @@ CHUNK_ELEMS = 4096
 ALL_BUCKETS = -1
 MAX_SLOTS = 4
 Q8_SLOT_BYTES = 4160
+FP4_SLOT_BYTES = 2176
 IPC_HANDLE_BYTES = 64
 DL_F32, DL_BF16, DL_F16, DL_U8 = 0, 1, 2, 3
 TUNE_NT_LOADS, TUNE_NT_STORES, TUNE_WT_STORES, TUNE_PAIRS = 1, 2, 8, 16
@@ -116,6 +117,15 @@ SIGNATURES = {
         ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
     ),
     "dl_unpack_adamw_q8": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp],
+    ),
+    "dl_delta_fp4": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "dl_fp4_reduce": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dl_unpack_sgd_fp4": (
+        ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
+    ),
+    "dl_unpack_adamw_fp4": (
         ctypes.c_int,
         [_vp, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp],
     ),

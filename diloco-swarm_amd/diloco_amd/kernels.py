@@ -20,6 +20,7 @@ _DT = {torch.float32: _lib.DL_F32, torch.bfloat16: _lib.DL_BF16}
 
 
 Q8_SLOT = _lib.Q8_SLOT_BYTES
+FP4_SLOT = _lib.FP4_SLOT_BYTES
 
 
 def wire_code(dtype: torch.dtype) -> int:
@@ -237,6 +238,31 @@ class HipKernels:
         exp_avg_sq (and the inner params), as unpack_adamw on the decoded values; scalars from
         adamw_scalars."""
         _lib.call("dl_unpack_adamw_q8", tree.handle, bucket, slots.data_ptr(), theta.data_ptr(),
+                  exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars, int(inner_slot),
+                  _s(theta))
+
+    # fp4 (MXFP4) wire codec (DL_FP4_SLOT_BYTES slots, one per chunk; dl_fp4.hip). residual
+    # None: no error feedback
+    def delta_fp4(self, tree, bucket, inner_slot, theta, residual, slots) -> None:
+        """slots <- enc(x), x = θ - inner (+ residual); residual <- x - deq(slots) in place."""
+        _lib.call("dl_delta_fp4", tree.handle, bucket, inner_slot, theta.data_ptr(),
+                  _ptr(residual), slots.data_ptr(), _s(theta))
+
+    def fp4_reduce(self, recv, n_peers, n_slots, divisor, residual, out) -> None:
+        """out <- enc((Σ_r deq(recv[r])) / divisor (+ residual)), r in rank order; residual (the
+        owner's n_slots * CHUNK_ELEMS floats) rewritten in place."""
+        _lib.call("dl_fp4_reduce", recv.data_ptr(), int(n_peers), int(n_slots), int(divisor),
+                  _ptr(residual), out.data_ptr(), _s(out))
+
+    def unpack_sgd_fp4(self, tree, bucket, slots, theta, mom, lr, momentum, nesterov, first,
+                       inner_slot) -> None:
+        _lib.call("dl_unpack_sgd_fp4", tree.handle, bucket, slots.data_ptr(), theta.data_ptr(),
+                  _ptr(mom), float(lr), float(momentum), int(nesterov), int(first),
+                  int(inner_slot), _s(theta))
+
+    def unpack_adamw_fp4(self, tree, bucket, slots, theta, exp_avg, exp_avg_sq, scalars,
+                         inner_slot) -> None:
+        _lib.call("dl_unpack_adamw_fp4", tree.handle, bucket, slots.data_ptr(), theta.data_ptr(),
                   exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars, int(inner_slot),
                   _s(theta))
 

@@ -47,6 +47,28 @@ ALL = _lib.ALL_BUCKETS
 S_CHUNK = _lib.CHUNK_ELEMS  # elements per tree chunk (one int8 slot each)
 
 
+def _decode_fp4(sl: torch.Tensor) -> torch.Tensor:
+    """[nch, DL_FP4_SLOT_BYTES] slots -> [nch, 4096] fp32, the values dl_unpack_*_fp4 form in
+    registers: ±grid[code]·2^(E-127), NaN for a group with E = 255. The bits are put together
+    with integer ops (code = 2·ee + mm is E2M1: exponent field ee, mantissa bit mm), so no
+    denormal passes through floating-point arithmetic."""
+    nch = sl.shape[0]
+    G = S_CHUNK // 32
+    e = sl[:, :G].to(torch.int32).repeat_interleave(32, dim=1)
+    pay = sl[:, G:].to(torch.int32)
+    nib = torch.stack((pay & 15, pay >> 4), dim=-1).reshape(nch, S_CHUNK)
+    code = nib & 7
+    # 2·grid[code] = (1 + half/2)·2^p with p = code >> 1 (code 1, the E2M1 subnormal, is 1·2^0)
+    half = (code & 1) * (code > 1)
+    be = (code >> 1) + e - 1  # the biased fp32 exponent of 2·grid[code]·2^(E-128)
+    normal = (be << 23) | (half << 22)
+    denormal = (2 + half) << (21 + be).clamp(min=0, max=21)  # be = 0 or -1 (E <= 1)
+    bits = torch.where(be >= 1, normal, denormal)
+    bits = torch.where(code == 0, torch.zeros_like(bits), bits | ((nib & 8) << 28))
+    bits = torch.where(e == 255, torch.full_like(bits, 0x7FC00000), bits)
+    return bits.view(torch.float32)
+
+
 def _check_host_params(params: Sequence[torch.Tensor]) -> None:
     for i, p in enumerate(params):
         if p.device.type != "cpu":
@@ -57,7 +79,11 @@ def _check_host_params(params: Sequence[torch.Tensor]) -> None:
 
 
 WRITE_BACKS = ("lazy", "sync", "deferred")
-OUTER_WIRES = ("f32", "bf16", "int8")
+OUTER_WIRES = ("f32", "bf16", "int8", "fp4")
+# The wires that send one fixed-size slot per tree chunk (q8_slot_plan; _all_reduce_q8): "int8"
+# (dl_q8.hip) and "fp4" (dl_fp4.hip, OCP MX block-scaled E2M1). They share the slot plan, the
+# exchange, its buffers and pipelining, and the residual arenas of error feedback.
+SLOT_WIRES = ("int8", "fp4")
 # The DP exchange behind sync_gradients for the device outer model at N > 1:
 #   "sharded"     per bucket RCCL reduce_scatter -> Nesterov SGD on this rank's 1/n of θ and
 #                 the momentum -> RCCL all_gather of θ (20 + 20/n B/param of HBM)
@@ -657,11 +683,12 @@ class DeviceOuterMirror:
             raise ValueError(f"wire {wire!r}: one of {OUTER_WIRES}")
         if exchange not in OUTER_EXCHANGES:
             raise ValueError(f"exchange {exchange!r}: one of {OUTER_EXCHANGES}")
-        if error_feedback and wire != "int8":
-            raise ValueError("error_feedback compensates the int8 wire's quantiser; it needs "
-                             "wire='int8'")
-        # int8 wire: every encode carries its residual (dl_delta_q8_ef) and the re-quantised
-        # average the owner's (dl_q8_reduce_ef); the arenas are made at the first exchange
+        if error_feedback and wire not in SLOT_WIRES:
+            raise ValueError("error_feedback compensates the int8 / fp4 wire's quantiser; it "
+                             "needs wire='int8' or wire='fp4'")
+        # int8 / fp4 wire: every encode carries its residual (dl_delta_q8_ef; dl_delta_fp4 with
+        # a residual) and the re-quantised average the owner's (dl_q8_reduce_ef; dl_fp4_reduce
+        # with one); the arenas, of one shape for both wires, are made at the first exchange
         self.error_feedback = bool(error_feedback)
         self._q8_res: Optional[torch.Tensor] = None
         self._q8_res_load: Optional[list] = None  # a loaded stage-2 state, until the buffers exist
@@ -1143,7 +1170,7 @@ class DeviceOuterMirror:
         """grad = Σ_peers grad / n (src/comm.py:120-123), in place on the packed .grad.
         ordered (DILOCO_DP_EXCHANGE=a2a): the rank-order sum, bit-exact at every n."""
         self.settle_state()
-        if self.wire == "int8":  # its exchange sums in rank order already (dl_q8_reduce)
+        if self.wire in SLOT_WIRES:  # their exchange sums in rank order already (dl_q8_reduce)
             self._all_reduce_q8(group, num_peers)
             return
         mode = self._exchange_mode(num_peers, ordered)
@@ -1260,9 +1287,28 @@ class DeviceOuterMirror:
         self._xmode, self._xgroup, self._xn, self._xrank = mode, group, n, rank
         self._div = n if mode == "sharded" else 1
 
-    # ---- the int8 wire behind the reference's calls ------------------------
+    # ---- the slot wires (int8: SURVEY §8f row 4; fp4) behind the reference's calls ------------
+    # One orchestration for both; the methods keep the int8 wire's names. The codec enters in
+    # four places: the slot size (_q8_buffers), the two lossy kernels (_slot_encode,
+    # _slot_reduce), the fused optimizer passes (_q8_sgd, _q8_adamw) and .grad's decode.
+    def _slot_encode(self, b: int, slot: int, theta, residual, region) -> None:
+        if self.wire == "fp4":
+            self.k.delta_fp4(self.tree, b, slot, theta, residual, region)
+        elif residual is not None:
+            self.k.delta_q8_ef(self.tree, b, slot, theta, residual, region)
+        else:
+            self.k.delta_q8(self.tree, b, slot, theta, region)
+
+    def _slot_reduce(self, recv, n: int, m: int, residual, red) -> None:
+        if self.wire == "fp4":
+            self.k.fp4_reduce(recv, n, m, n, residual, red)
+        elif residual is not None:
+            self.k.q8_reduce_ef(recv, n, m, n, residual, red)
+        else:
+            self.k.q8_reduce(recv, n, m, n, red)
+
     def _q8_buffers(self, n: int) -> dict:
-        """Slot regions of every bucket (n·m slots of Q8_SLOT bytes: the bucket's chunks in
+        """Slot regions of every bucket (n·m slots of the wire's slot size: the bucket's chunks in
         order, zero padding to a multiple of n), two all_to_all landing buffers, one reduced
         region per bucket (so every bucket's all_gather may stay in flight). Error feedback:
         the stage-2 residual of the reduced regions, zero whenever the buffers are (re)built
@@ -1270,17 +1316,18 @@ class DeviceOuterMirror:
         q = getattr(self, "_q8", None)
         if q is not None and q["n"] == n:
             return q
-        from .kernels import Q8_SLOT
+        from .kernels import FP4_SLOT, Q8_SLOT
 
+        S = FP4_SLOT if self.wire == "fp4" else Q8_SLOT  # the slot size is the codec's
         plan, base, rbase, mmax = q8_slot_plan(self.tree.bucket_chunks, n)
         z = dict(dtype=torch.uint8, device=self.device)
         segs = []
         for lo, hi in self.tree.bucket_ranges:
             segs.append([i for i, o in enumerate(self.offs) if lo <= o < hi])
-        self._q8 = q = {"n": n, "plan": plan, "S": Q8_SLOT, "segs": segs,
-                        "slots": torch.zeros(base * Q8_SLOT, **z),
-                        "red": torch.zeros(rbase * Q8_SLOT, **z),
-                        "recv": [torch.zeros(n * mmax * Q8_SLOT, **z) for _ in range(2)]}
+        self._q8 = q = {"n": n, "plan": plan, "S": S, "segs": segs,
+                        "slots": torch.zeros(base * S, **z),
+                        "red": torch.zeros(rbase * S, **z),
+                        "recv": [torch.zeros(n * mmax * S, **z) for _ in range(2)]}
         if self.error_feedback:
             q["res"] = torch.zeros(rbase * S_CHUNK, dtype=torch.float32, device=self.device)
             load, self._q8_res_load = self._q8_res_load, None
@@ -1304,7 +1351,8 @@ class DeviceOuterMirror:
 
     def q8_ef_state(self) -> Optional[dict]:
         """{"encode": the encoder's residual, "reduce": [this peer's stage-2 residual per
-        bucket]} as clones; None when error feedback is off or no exchange has run yet."""
+        bucket]} as clones; None when error feedback is off or no exchange has run yet. The
+        int8 and the fp4 wire keep the same arenas (fp32, the same shapes): one accessor pair."""
         if not self.error_feedback or self._q8_res is None:
             return None
         self._join()
@@ -1356,7 +1404,9 @@ class DeviceOuterMirror:
         pass dequantises inside dl_unpack_sgd_q8; .grad shows the decoded average when read.
         Eager: decoded into .grad at once. With error feedback both kernels are their _ef
         forms: every encode (either path) carries this rank's residual, the reduce its owner's;
-        the slots, and so the optimizer passes and .grad, are used as without it."""
+        the slots, and so the optimizer passes and .grad, are used as without it.
+        wire="fp4": the same walk with dl_delta_fp4, dl_fp4_reduce and dl_unpack_*_fp4 on
+        2176-B slots (_slot_encode, _slot_reduce); a residual handed in is error feedback."""
         if self._delta is not None:
             self._take_delta()
             self._relay_theta()
@@ -1380,11 +1430,8 @@ class DeviceOuterMirror:
         if ef and self._q8_res is None:
             self._q8_res = torch.zeros(self.tree.total, dtype=torch.float32, device=self.device)
 
-        def pack(b):
-            if ef:  # both encode paths carry the residual
-                self.k.delta_q8_ef(self.tree, b, slot, theta, self._q8_res, self._q8_region(q, b))
-            else:
-                self.k.delta_q8(self.tree, b, slot, theta, self._q8_region(q, b))
+        def pack(b):  # with error feedback both encode paths carry the residual
+            self._slot_encode(b, slot, theta, self._q8_res if ef else None, self._q8_region(q, b))
 
         def a2a(b):
             nch, m, _, _ = q["plan"][b]
@@ -1401,11 +1448,8 @@ class DeviceOuterMirror:
             pend[b].wait()
             nch, m, _, rb = q["plan"][b]
             red = q["red"][rb * S:(rb + m) * S]
-            if ef:
-                self.k.q8_reduce_ef(q["recv"][b % 2][:n * m * S], n, m, n,
-                                    self._q8_reduce_residual(q, b), red)
-            else:
-                self.k.q8_reduce(q["recv"][b % 2][:n * m * S], n, m, n, red)
+            self._slot_reduce(q["recv"][b % 2][:n * m * S], n, m,
+                              self._q8_reduce_residual(q, b) if ef else None, red)
             works[b] = dist.all_gather_into_tensor(self._q8_region(q, b), red, group=group,
                                                    async_op=True)
         self._works = works
@@ -1424,8 +1468,11 @@ class DeviceOuterMirror:
         for b in range(self.tree.n_buckets):
             nch, m, base, _ = q["plan"][b]
             sl = q["slots"][base * S:(base + nch) * S].view(nch, S)
-            g = sl[:, S - C:].contiguous().view(torch.int8).float() * \
-                sl[:, :4].contiguous().view(torch.float32)
+            if self.wire == "fp4":
+                g = _decode_fp4(sl)
+            else:
+                g = sl[:, S - C:].contiguous().view(torch.int8).float() * \
+                    sl[:, :4].contiguous().view(torch.float32)
             r = 0
             for i in q["segs"][b]:
                 n_i = self.numels[i]
@@ -1444,8 +1491,9 @@ class DeviceOuterMirror:
         for b in range(self.tree.n_buckets):
             if works is not None:
                 works[b].wait()
-            self.k.unpack_sgd_q8(self.tree, b, self._q8_region(q, b), self.d_theta, mom, lr,
-                                 momentum, nesterov, first, SLOT_INNER if write else -1)
+            step = self.k.unpack_sgd_fp4 if self.wire == "fp4" else self.k.unpack_sgd_q8
+            step(self.tree, b, self._q8_region(q, b), self.d_theta, mom, lr, momentum, nesterov,
+                 first, SLOT_INNER if write else -1)
         # the slots keep the average for a later .grad read (_xmode stays "q8")
 
     def _q8_adamw(self, scalars, target) -> None:
@@ -1460,8 +1508,9 @@ class DeviceOuterMirror:
         for b in range(self.tree.n_buckets):
             if works is not None:
                 works[b].wait()
-            self.k.unpack_adamw_q8(self.tree, b, self._q8_region(q, b), self.d_theta, self.d_m1,
-                                   self.d_m2, scalars, SLOT_INNER if write else -1)
+            step = self.k.unpack_adamw_fp4 if self.wire == "fp4" else self.k.unpack_adamw_q8
+            step(self.tree, b, self._q8_region(q, b), self.d_theta, self.d_m1, self.d_m2, scalars,
+                 SLOT_INNER if write else -1)
         # the slots keep the average for a later .grad read (_xmode stays "q8")
 
     def _launch_reductions(self, pack, view, group) -> None:

@@ -118,7 +118,8 @@ class OuterAdamW(AdamW):
     dl_shard_adamw per bucket on this rank's 1/n, after the rank-order one
     (DILOCO_DP_EXCHANGE=a2a, bit-exact at every replica count) one dl_shard_reduce_adamw, each
     followed by the all_gather of θ; after the int8 exchange (wire="int8") one
-    dl_unpack_adamw_q8 per bucket on the averaged slots, the whole tree on every rank. It IS a torch.optim.AdamW (param_groups, hooks, LR
+    dl_unpack_adamw_q8 per bucket on the averaged slots, the whole tree on every rank (the fp4
+    exchange, wire="fp4": dl_unpack_adamw_fp4 in its place). It IS a torch.optim.AdamW (param_groups, hooks, LR
     schedulers and state_dict work unchanged; state[p]["step"] is torch's fp32 scalar tensor,
     exp_avg and exp_avg_sq are views of the mirror's packed arenas), selected by get_optimizer
     under DILOCO_OUTER_ADAMW=fused. After a sharded or rank-order step each rank holds its own

@@ -57,7 +57,10 @@ and sync_inner_model a verified no-op after the step; wire (DILOCO_OUTER_WIRE, "
 "bf16": BASELINE config #5's codec on the DP exchange; "int8": one scale per 4096-element
 chunk, and with error_feedback (DILOCO_OUTER_Q8_EF, off if unset) both of its quantisers
 carry what they round away into the next outer step: dl_delta_q8_ef, dl_q8_reduce_ef;
-q8_error_feedback_state / load_q8_error_feedback_state); exchange (DILOCO_OUTER_EXCHANGE;
+q8_error_feedback_state / load_q8_error_feedback_state; "fp4": the same exchange at 4 bits,
+OCP MX block-scaled E2M1 in 2176-B slots, 0.531 B/param -- dl_delta_fp4, dl_fp4_reduce,
+dl_unpack_sgd_fp4 / dl_unpack_adamw_fp4 -- with error_feedback from DILOCO_OUTER_FP4_EF, off if
+unset, and the same two state helpers); exchange (DILOCO_OUTER_EXCHANGE;
 "replicated", the host placement's default: all_reduce -> the SGD pass on every rank, so
 .grad and the momentum are local on every rank as in the reference; "sharded", the device
 placement's default: reduce_scatter -> SGD on this rank's 1/n -> all_gather of θ, SURVEY §8e;
@@ -78,7 +81,7 @@ import torch.nn as nn
 from torch.optim import SGD, AdamW, Optimizer
 
 from .kernels import default_kernels
-from .mirror import (DEFAULT_EXCHANGE, OUTER_EXCHANGES, OUTER_WIRES, WRITE_BACKS,
+from .mirror import (DEFAULT_EXCHANGE, OUTER_EXCHANGES, OUTER_WIRES, SLOT_WIRES, WRITE_BACKS,
                      DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
 from .optim import InnerAdamW, OuterAdamW, OuterSGD
 from ._lib import ALL_BUCKETS
@@ -217,13 +220,15 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     built while the inner model is on the CPU, it stays there until the first
     compute_pseudo_gradient names the device); write_back "lazy" (default: the host outer
     model stepped on an HBM twin), "sync" or "deferred" for the host placement; fused
-    (default on), wire ("f32" default, "bf16": BASELINE config #5's codec; "int8") and
+    (default on), wire ("f32" default, "bf16": BASELINE config #5's codec; "int8"; "fp4") and
     exchange ("replicated" for the host placement and "sharded" for placement="device" by
     default, or "a2a") for placement="device" and for the lazy host write-back (see the module
     docstring). error_feedback (int8 wire only; None reads DILOCO_OUTER_Q8_EF, default off):
     both quantisers of the int8 exchange carry what they round away into the next outer step
     (dl_delta_q8_ef, dl_q8_reduce_ef); q8_error_feedback_state / load_q8_error_feedback_state
-    let a checkpoint carry the residuals."""
+    let a checkpoint carry the residuals. The fp4 wire takes error_feedback too (None reads
+    DILOCO_OUTER_FP4_EF, default off): dl_delta_fp4 and dl_fp4_reduce with their residuals, the
+    same arenas and the same two state helpers."""
     if placement is None:
         placement = os.environ.get("DILOCO_OUTER_PLACEMENT", "host")
     if placement not in PLACEMENTS:
@@ -238,11 +243,12 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
         wire = os.environ.get("DILOCO_OUTER_WIRE", "f32")
     if wire not in OUTER_WIRES:
         raise ValueError(f"wire {wire!r}: one of {OUTER_WIRES}")
-    if error_feedback is None:  # the variable is consulted for the int8 wire only
-        error_feedback = wire == "int8" and env_flag("DILOCO_OUTER_Q8_EF", False)
-    elif error_feedback and wire != "int8":
-        raise ValueError(f"error_feedback=True compensates the int8 wire's quantiser; the wire "
-                         f"is {wire!r}")
+    if error_feedback is None:  # each variable is consulted for its own wire only
+        error_feedback = ((wire == "int8" and env_flag("DILOCO_OUTER_Q8_EF", False))
+                          or (wire == "fp4" and env_flag("DILOCO_OUTER_FP4_EF", False)))
+    elif error_feedback and wire not in SLOT_WIRES:
+        raise ValueError(f"error_feedback=True compensates the int8 / fp4 wire's quantiser; the "
+                         f"wire is {wire!r}")
     if exchange is None:
         exchange = os.environ.get("DILOCO_OUTER_EXCHANGE") or None
     asked = exchange is not None
@@ -301,7 +307,8 @@ def _q8_ef_mirror(outer_model: nn.Module):
 
 
 def q8_error_feedback_state(outer_model: nn.Module):
-    """The int8 wire's error-feedback residuals of this rank, for a checkpoint:
+    """The int8 or fp4 wire's error-feedback residuals of this rank (both wires keep the same
+    fp32 arenas, so one pair of helpers serves both), for a checkpoint:
     {"encode": the encoder's residual (packed layout), "reduce": [the residual of this rank's
     re-quantised slots, per bucket]} as clones. None when the feature is off or no exchange has
     run yet. The residuals are per rank (they are what this rank has not sent yet)."""

@@ -36,6 +36,7 @@ extern "C" {
 #define DL_ALL_BUCKETS (-1)
 #define DL_MAX_SLOTS 4         /* per-tensor pointer tables per tree */
 #define DL_Q8_SLOT_BYTES 4160  /* int8 wire: 64-B header (fp32 scale) + DL_CHUNK_ELEMS int8 */
+#define DL_FP4_SLOT_BYTES 2176 /* fp4 wire: DL_CHUNK_ELEMS/32 scale bytes + DL_CHUNK_ELEMS/2 */
 
 /* wire / packed dtypes */
 #define DL_F32 0
@@ -457,6 +458,65 @@ DL_API int dl_gather_q8_ef(dl_tree_t tree, int32_t bucket, int32_t src_slot,
                            float* residual_packed, void* slots, dl_stream_t stream);
 DL_API int dl_unpack_avg_q8(dl_tree_t tree, int32_t bucket, const void* slots, int32_t dst_slot,
                             double* partials, dl_stream_t stream);
+
+/* ---- fp4 wire codec (OCP MX block-scaled E2M1, "MXFP4"; not in the reference) -----------
+ * The pseudo-gradient exchange of the int8 wire at 4 bits: the same slot plan, collectives and
+ * residual arenas, 0.531 B/param. One DL_FP4_SLOT_BYTES slot per chunk of the bucket, in chunk
+ * order:
+ *   bytes [0, 128)     one scale byte E per group g of 32 elements [32g, 32g + 32)
+ *   bytes [128, 2176)  element i in byte 128 + i/2, low nibble for even i, high for odd i
+ * A nibble is sign << 3 | code, code indexing {0, 0.5, 1, 1.5, 2, 3, 4, 6}. Elements past the
+ * chunk's length count as +0: groups wholly past it are zero bytes, and an all-zero (padding)
+ * slot decodes to zeros. The encoder and the reduce write every byte of each slot they are
+ * launched on, whatever it held before, and no byte of any other slot.
+ * Scale of a group, A = max over the group of (bits(x) & 0x7fffffff) as an unsigned integer
+ * (monotone in |x|; a NaN is not dropped):
+ *   A >= 0x7f800000 (a NaN or Inf in the group): E = 255, all 32 nibbles 0
+ *   A == 0: E = 0, nibbles 0
+ *   else, amax = float(A) = m * 2^k with m in [0.5, 1): e = k - 3 if m <= 0.75, else k - 2 --
+ *   the smallest e with amax * 2^-e <= 6, so nothing saturates (the OCP rule
+ *   floor(log2 amax) - 2 clamps amax * 2^-e in (6, 8)); E = max(0, e + 127) <= 253. A denormal
+ *   amax is a value like any other.
+ * Element: y = |x| * 2^(127 - E); code = the grid point nearest y, ties to the even code
+ * (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); the sign bit is set
+ * only when code != 0 (nibble 8 never occurs).
+ * Decode: E == 255: NaN for the group's 32 elements; else +-grid[code] * 2^(E - 127), exact in
+ * fp32 for every E (2^-128, a denormal, is the smallest value; nothing flushes it). So
+ * |x - deq| <= 2^(E - 127) < amax / 3 (E > 0), and deq(enc(deq(s))) == deq(s) bit for bit.
+ * dl_delta_fp4, per chunk c of the bucket and element k of the packed space:
+ *   x = outer[k] - inner[seg][j]           (residual_packed NULL)
+ *   x = (outer[k] - inner[seg][j]) + r[k]  (r = residual_packed: two rounded fp32 operations)
+ *   slot(c) <- enc(x);  r[k] <- x - deq(slot(c))   (one subtract, in place, by the same lane)
+ * Nothing of θ, inner or r is loaded or stored past a chunk's length. Results do not depend on
+ * the inner tensors' alignment, the grid or the bucket split. A non-finite group leaves NaN
+ * residuals for its 32 elements until the caller resets the residual. 8.53 B/param (16.53 with
+ * the residual).
+ * dl_fp4_reduce, on the owner of n_slots slots (recv laid out [peer][slot]):
+ *   acc = 0; acc = acc + deq(recv[r][j]) for r in rank order; if divisor > 1: acc /= divisor
+ *   x = acc (+ r2[j*DL_CHUNK_ELEMS + i], residual not NULL);  out slot j <- enc(x);
+ *   r2[...] <- x - deq(out slot j)         (all DL_CHUNK_ELEMS values of every slot)
+ * out may alias recv only at n_peers == 1. Every peer receives byte-identical averaged slots.
+ * (n_peers + 1) * 0.531 B per owned param (+ 8 with the residual).
+ * dl_unpack_sgd_fp4 / dl_unpack_adamw_fp4: g = deq(slot), then one element of dl_unpack_sgd /
+ * dl_unpack_adamw (divisor 1) and inner[seg][j] = θ (inner_slot < 0: no inner write): bit-
+ * identical to decoding the slots into an fp32 wire and running those on it. The slots are only
+ * read; nothing is stored past a chunk's length. 20.53 and 28.53 B/param (24.53 for AdamW
+ * without the inner write). slots, outer, the state pointers (and a residual that is given)
+ * 16-B aligned. */
+DL_API int dl_delta_fp4(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
+                        const float* outer_packed, float* residual_packed /* NULL: no EF */,
+                        void* slots, dl_stream_t stream);
+DL_API int dl_fp4_reduce(const void* recv, int32_t n_peers, int32_t n_slots, int32_t divisor,
+                         float* residual /* NULL: no EF */, void* out, dl_stream_t stream);
+DL_API int dl_unpack_sgd_fp4(dl_tree_t tree, int32_t bucket, const void* slots,
+                             float* outer_packed, float* mom_packed, float lr, float momentum,
+                             int32_t nesterov, int32_t first_step, int32_t inner_slot,
+                             dl_stream_t stream);
+DL_API int dl_unpack_adamw_fp4(dl_tree_t tree, int32_t bucket, const void* slots,
+                               float* outer_packed, float* exp_avg_packed,
+                               float* exp_avg_sq_packed, float decay, float w1, float beta2,
+                               float w2, float neg_step_size, float bc2_sqrt, float eps,
+                               int32_t inner_slot, dl_stream_t stream);
 
 /* ---- serializer (src/serializer.py:11-15) ----------------------------------------------
  * out is fp32 of 2*numel elements: out[0] = meta0, out[1] = meta1, out[numel + i] =
