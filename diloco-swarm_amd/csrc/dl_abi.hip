@@ -1174,6 +1174,34 @@ DL_API int dl_unpack_avg_q8(dl_tree_t t, int32_t b, const void* slots, int32_t d
                          : hip_fail(e, "dl_unpack_avg_q8");
 }
 
+// The gradient side of the fp4 exchange (dl_fp4_grad.hip): the checks, launches and policies of
+// the int8 calls above; a null residual selects the encoder without error feedback.
+DL_API int dl_gather_fp4(dl_tree_t t, int32_t b, int32_t src_slot, float* residual, void* slots,
+                         dl_stream_t s) {
+  dl::Launch L;
+  if (residual) DL_TRY(check_packed(residual, "dl_gather_fp4", "residual"));
+  DL_TRY(check_packed(slots, "dl_gather_fp4", "slots"));
+  DL_TRY(make_launch(t, b, s, &L, "dl_gather_fp4", kAutoDeltaQ8));
+  DL_TRY(check_slot(t, src_slot, "dl_gather_fp4"));
+  DL_TRY(slot_begin(t, src_slot, L.stream, "dl_gather_fp4"));
+  hipError_t e = dl::launch_gather_fp4(L, src_slot, residual, static_cast<uint8_t*>(slots));
+  return e == hipSuccess ? slot_end(t, src_slot, L.stream, "dl_gather_fp4")
+                         : hip_fail(e, "dl_gather_fp4");
+}
+
+DL_API int dl_unpack_avg_fp4(dl_tree_t t, int32_t b, const void* slots, int32_t dst_slot,
+                             double* partials, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_packed(slots, "dl_unpack_avg_fp4", "slots"));
+  if (partials) DL_TRY(check_partials(partials, "dl_unpack_avg_fp4"));
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_avg_fp4", kAutoNT, Big::two_chunks));
+  DL_TRY(check_slot(t, dst_slot, "dl_unpack_avg_fp4"));
+  DL_TRY(slot_begin(t, dst_slot, L.stream, "dl_unpack_avg_fp4"));
+  hipError_t e = dl::launch_unpack_avg_fp4(L, static_cast<const uint8_t*>(slots), dst_slot, partials);
+  return e == hipSuccess ? slot_end(t, dst_slot, L.stream, "dl_unpack_avg_fp4")
+                         : hip_fail(e, "dl_unpack_avg_fp4");
+}
+
 DL_API int dl_norm_finish(const double* partials, int32_t n_partials, float max_norm, float* out2,
                           dl_stream_t s) {
   if (n_partials < 0) return fail(DL_E_ARG, "dl_norm_finish: n_partials %d", n_partials);

@@ -118,6 +118,11 @@ hipError_t launch_unpack_sgd_fp4(const Launch& L, const uint8_t* slots, float* o
                                  SgdArgs a, int inner_slot);
 hipError_t launch_unpack_adamw_fp4(const Launch& L, const uint8_t* slots, float* outer, float* m1,
                                    float* m2, AdamArgs a, int inner_slot);
+// the gradient side of the fp4 exchange (dl_fp4_grad.hip): launch_gather_q8 /
+// launch_unpack_avg_q8 on the fp4 slots
+hipError_t launch_gather_fp4(const Launch& L, int src_slot, float* resid, uint8_t* slots);
+hipError_t launch_unpack_avg_fp4(const Launch& L, const uint8_t* slots, int dst_slot,
+                                 double* partials);
 hipError_t launch_unpack_adamw(const Launch& L, const void* wire, int wire_dtype, int divisor,
                                float* outer, float* m1, float* m2, AdamArgs a, int inner_slot);
 hipError_t launch_delta_pack_adamw(const Launch& L, int inner_slot, float* outer, void* wire,

@@ -132,6 +132,8 @@ SIGNATURES = {
     "dl_gather_q8": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "dl_gather_q8_ef": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "dl_unpack_avg_q8": (ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _vp]),
+    "dl_gather_fp4": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "dl_unpack_avg_fp4": (ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _vp]),
     "dl_gather": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, _vp]),
     "dl_scatter": (ctypes.c_int, [_vp, _i32, _vp, _i32, _vp]),
     "dl_serialize": (ctypes.c_int, [_vp, _i32, _i64, _f32, _f32, _vp, _vp]),

@@ -156,17 +156,24 @@ DP_EXCHANGE = os.environ.get("DILOCO_DP_EXCHANGE", "rccl")
 # The wire of the device-gradient GradSync (only that branch: the outer model's mirror has its
 # own, DILOCO_OUTER_WIRE, and the host loop none): "f32", "bf16", or "int8" -- the outer step's
 # int8 codec on the per-step exchange, 2(n-1)/n * 1.016 bus bytes per parameter against
-# 8(n-1)/n, with DP_Q8_EF (consulted for int8 only, off if unset) both quantisers' error feedback
-DP_WIRES = {"f32": torch.float32, "bf16": torch.bfloat16, "int8": torch.int8}
+# 8(n-1)/n, with DP_Q8_EF (consulted for int8 only, off if unset) both quantisers' error feedback;
+# or "fp4" -- the outer step's MXFP4 codec there, 2(n-1)/n * 0.531 bus bytes per parameter, with
+# DP_FP4_EF (DILOCO_DP_FP4_EF; consulted for fp4 only, off if unset). No torch dtype names the
+# fp4 format on every build, so GradSync takes the string
+DP_WIRES = {"f32": torch.float32, "bf16": torch.bfloat16, "int8": torch.int8, "fp4": "fp4"}
 DP_WIRE = os.environ.get("DILOCO_DP_WIRE", "f32")
-DP_Q8_EF = os.environ.get("DILOCO_DP_Q8_EF", "0").strip().lower() in ("1", "true", "yes", "on")
+_ON = ("1", "true", "yes", "on")
+DP_Q8_EF = os.environ.get("DILOCO_DP_Q8_EF", "0").strip().lower() in _ON
+DP_FP4_EF = os.environ.get("DILOCO_DP_FP4_EF", "0").strip().lower() in _ON
 
 
 def dp_wire():
-    """(wire dtype, error feedback) of the GradSync that DPSync builds, from DP_WIRE / DP_Q8_EF."""
+    """(wire dtype, error feedback) of the GradSync that DPSync builds, from DP_WIRE and the
+    wire's own error-feedback knob (DP_Q8_EF for int8, DP_FP4_EF for fp4)."""
     if DP_WIRE not in DP_WIRES:
         raise ValueError(f"DILOCO_DP_WIRE {DP_WIRE!r}: one of {tuple(DP_WIRES)}")
-    return DP_WIRES[DP_WIRE], DP_WIRE == "int8" and bool(DP_Q8_EF)
+    ef = {"int8": DP_Q8_EF, "fp4": DP_FP4_EF}.get(DP_WIRE, False)
+    return DP_WIRES[DP_WIRE], bool(ef)
 
 
 class DPSync:

@@ -29,11 +29,20 @@ decode -- only the encoder's residual. A NaN/Inf gradient leaves a non-finite re
 rules, as in the outer codec) until load_q8_ef_state(None) resets it. The residuals belong to
 this GradSync: one rebuilt for other parameters starts from zero.
 
+wire_dtype="fp4" (the string: no torch dtype names the format on every build): the same slot
+exchange with the outer step's 4-bit codec (dl_fp4.hip; one DL_FP4_SLOT_BYTES slot per chunk, the
+same slot plan) -- per bucket dl_gather_fp4 -> all_to_all -> dl_fp4_reduce (divisor n) ->
+all_gather -> dl_unpack_avg_fp4: 2(n-1)/n · 0.531 bus bytes per parameter. error_feedback=True
+hands the same two residual arenas to dl_gather_fp4 and dl_fp4_reduce (q8_ef_state /
+load_q8_ef_state serve both slot wires). One replica: encode, dl_fp4_reduce of the region onto
+itself (the identity: deq(enc(deq(s))) == deq(s)), decode. The two slot wires differ in their
+slot size and their three calls only (SLOT_WIRES).
+
 sync(max_norm): the clip_grad_norm_ that follows the sync in the training loop
 (src/train.py:255), fused into it. Every dl_unpack_avg becomes dl_unpack_avg_sumsq, which holds
 each averaged gradient in registers on its way to .grad and leaves the chunk's Σ g²; after the
 last bucket dl_norm_finish and one dl_scale_by run on the same stream (int8 wire:
-dl_unpack_avg_q8 leaves the same partial sums). Equal, bit for bit, to
+dl_unpack_avg_q8, fp4 wire: dl_unpack_avg_fp4 leave the same partial sums). Equal, bit for bit, to
 sync() followed by utils.clip_grad_norm_, without that call's read of every gradient.
 """
 from __future__ import annotations
@@ -43,15 +52,20 @@ from typing import Optional, Sequence
 import torch
 import torch.distributed as dist
 
-from .kernels import Q8_SLOT, default_kernels
+from .kernels import FP4_SLOT, Q8_SLOT, default_kernels
 from . import _lib
 from .outer import _Done, pipelined_buckets
 from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_GRAD, q8_slot_plan
 
 
+# The slot wires: wire_dtype -> slot bytes. Each has a three-call codec (encode, reduce, decode;
+# GradSync._codec), as the mirror's SLOT_WIRES; everything between the calls is shared.
+SLOT_WIRES = {torch.int8: Q8_SLOT, "fp4": FP4_SLOT}
+
+
 class GradSync:
     def __init__(self, params: Sequence[torch.Tensor], group: Optional[dist.ProcessGroup],
-                 world_size: int, wire_dtype: torch.dtype = torch.float32,
+                 world_size: int, wire_dtype=torch.float32,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, kernels=None,
                  exchange: str = "rccl", error_feedback: bool = False):
         self.params = list(params)
@@ -61,16 +75,21 @@ class GradSync:
         if exchange not in ("rccl", "a2a"):
             raise ValueError(f"exchange {exchange!r}: 'rccl' or 'a2a'")
         self.a2a = exchange == "a2a"
+        if isinstance(wire_dtype, str) and wire_dtype != "fp4":
+            raise ValueError(f"wire_dtype {wire_dtype!r}: a torch dtype or 'fp4'")
         self.q8 = wire_dtype == torch.int8
-        # int8 wire only: carry what each quantiser rounds away into the next sync
-        # (dl_gather_q8_ef, dl_q8_reduce_ef)
+        self.fp4 = wire_dtype == "fp4"
+        # a slot wire (int8, fp4): the bytes of one chunk's slot; None on the flat wires
+        self.slot_bytes = SLOT_WIRES.get(wire_dtype)
+        # slot wires only: carry what each quantiser rounds away into the next sync
+        # (dl_gather_q8_ef, dl_q8_reduce_ef; dl_gather_fp4 / dl_fp4_reduce with a residual)
         self.error_feedback = bool(error_feedback)
-        if self.error_feedback and not self.q8:
-            raise ValueError("error_feedback compensates the int8 wire's quantiser; it needs "
-                             "wire_dtype=torch.int8")
-        if self.q8 and self.a2a:
-            raise ValueError("the int8 wire has its own rank-order exchange; exchange='a2a' "
-                             "averages the fp32 grads")
+        if self.error_feedback and self.slot_bytes is None:
+            raise ValueError("error_feedback compensates the int8 / fp4 wire's quantiser; it "
+                             "needs wire_dtype=torch.int8 or 'fp4'")
+        if self.slot_bytes is not None and self.a2a:
+            raise ValueError(f"the {'fp4' if self.fp4 else 'int8'} wire has its own rank-order "
+                             "exchange; exchange='a2a' averages the fp32 grads")
         if dist.is_initialized() and self.world_size > 1:
             gs = dist.get_world_size(group)
             if gs != self.world_size:  # the collectives would reduce over the wrong ranks
@@ -87,9 +106,9 @@ class GradSync:
         # a2a: buckets split into n equal 64-element-aligned shards
         balign = _lib.ALIGN_ELEMS * (self.world_size if self.a2a else 1)
         self.tree = self.k.tree(self.numels, self.device, bucket_cap_elems, balign)
-        if self.q8:
+        if self.slot_bytes is not None:
             self.wire = None
-            self._alloc_q8()
+            self._alloc_slots()
         else:
             self.wire = torch.zeros(self.tree.total, dtype=wire_dtype, device=self.device)
         if self.a2a:
@@ -104,17 +123,17 @@ class GradSync:
         self.stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
         self.partials = None  # per-chunk Σ g² of sync(max_norm), created on first use
 
-    def _alloc_q8(self) -> None:
+    def _alloc_slots(self) -> None:
         """OuterSync's slot plan: a region of n * m_b slots per bucket, zero at allocation (the
         padding slots are never encoded), landing and reduce buffers for two buckets in flight."""
-        n = self.world_size
+        n, S = self.world_size, self.slot_bytes
         self.q8_plan, total, _owned, mmax = q8_slot_plan(self.tree.bucket_chunks, n)
         z = dict(dtype=torch.uint8, device=self.device)
-        self.q_slots = torch.zeros(total * Q8_SLOT, **z)
+        self.q_slots = torch.zeros(total * S, **z)
         self.q_recv = self.q_red = None
         if not self.local:
-            self.q_recv = [torch.zeros(n * mmax * Q8_SLOT, **z) for _ in range(2)]
-            self.q_red = [torch.zeros(mmax * Q8_SLOT, **z) for _ in range(2)]
+            self.q_recv = [torch.zeros(n * mmax * S, **z) for _ in range(2)]
+            self.q_red = [torch.zeros(mmax * S, **z) for _ in range(2)]
         # error feedback: the encoder's residual in the packed layout, and at n > 1 the
         # residual of this peer's m_b re-quantised slots of every bucket
         self.q_residual = self.q_residual_red = None
@@ -126,13 +145,16 @@ class GradSync:
                                        for _nch, m, _at, _rat in self.q8_plan]
 
     def q8_region(self, bucket: int) -> torch.Tensor:
-        """The int8 slots of one bucket (n * m slots, chunk order, zero padding at the end)."""
+        """The int8 / fp4 slots of one bucket (n * m slots, chunk order, zero padding at the
+        end)."""
         _nch, m, at, _rat = self.q8_plan[bucket]
-        return self.q_slots[at * Q8_SLOT:(at + self.world_size * m) * Q8_SLOT]
+        S = self.slot_bytes
+        return self.q_slots[at * S:(at + self.world_size * m) * S]
 
     def q8_ef_state(self) -> Optional[dict]:
         """{"encode": the encoder's residual, "reduce": [this peer's stage-2 residual per
-        bucket]} as clones (the mirror's q8_ef_state); None when error feedback is off."""
+        bucket]} as clones (the mirror's q8_ef_state); None when error feedback is off. The
+        int8 and the fp4 wire keep the same arenas (fp32, the same shapes): one accessor pair."""
         if not self.error_feedback:
             return None
         return {"encode": self.q_residual.clone(),
@@ -217,8 +239,8 @@ class GradSync:
         # one replica (self.local): the all-reduce is the identity (the rebinding, gather and
         # /1 still run, so the path is exercised on a one-GPU machine)
         local = self.local
-        if self.q8:
-            self._sync_q8(clip)
+        if self.slot_bytes is not None:
+            self._sync_slots(clip)
             return
         if self.a2a and not local:
             self._sync_a2a(clip)
@@ -265,21 +287,39 @@ class GradSync:
         ag[nb - 1].wait()
         self._unpack(nb - 1, 1, clip)
 
-    def _sync_q8(self, clip=None) -> None:
-        """gather_q8(b) -> all_to_all(b) | q8_reduce(b) -> all_gather(b) | unpack_avg_q8(b),
-        overlapped across buckets like _sync_a2a; the landing and reduce buffers alternate, so
-        the bytes do not depend on the overlap."""
-        n, nb = self.world_size, self.tree.n_buckets
-        partials = None if clip is None else self.partials
+    def _codec(self):
+        """(encode(b), reduce(recv, n, m, divisor, residual, out), decode(b, partials)) of this
+        slot wire; residual None: the call without error feedback."""
+        k, tree = self.k, self.tree
+        resid = self.q_residual  # None without error feedback
+        if self.fp4:
+            return (lambda b: k.gather_fp4(tree, b, SLOT_GRAD, resid, self.q8_region(b)),
+                    k.fp4_reduce,
+                    lambda b, p: k.unpack_avg_fp4(tree, b, self.q8_region(b), SLOT_GRAD, p))
 
         def encode(b):
-            if self.error_feedback:
-                self.k.gather_q8_ef(self.tree, b, SLOT_GRAD, self.q_residual, self.q8_region(b))
+            if resid is not None:
+                k.gather_q8_ef(tree, b, SLOT_GRAD, resid, self.q8_region(b))
             else:
-                self.k.gather_q8(self.tree, b, SLOT_GRAD, self.q8_region(b))
+                k.gather_q8(tree, b, SLOT_GRAD, self.q8_region(b))
 
-        def decode(b):
-            self.k.unpack_avg_q8(self.tree, b, self.q8_region(b), SLOT_GRAD, partials)
+        def reduce(recv, n, m, divisor, residual, out):
+            if residual is not None:
+                k.q8_reduce_ef(recv, n, m, divisor, residual, out)
+            else:
+                k.q8_reduce(recv, n, m, divisor, out)
+
+        return encode, reduce, lambda b, p: k.unpack_avg_q8(tree, b, self.q8_region(b),
+                                                            SLOT_GRAD, p)
+
+    def _sync_slots(self, clip=None) -> None:
+        """encode(b) -> all_to_all(b) | reduce(b) -> all_gather(b) | decode(b) with the wire's
+        three calls (_codec: gather_q8 / q8_reduce / unpack_avg_q8, or their fp4 twins),
+        overlapped across buckets like _sync_a2a; the landing and reduce buffers alternate, so
+        the bytes do not depend on the overlap."""
+        n, nb, S = self.world_size, self.tree.n_buckets, self.slot_bytes
+        partials = None if clip is None else self.partials
+        encode, reduce, decode = self._codec()
 
         if self.local:
             # one replica: the average of one is its own re-quantised slots (error feedback:
@@ -288,14 +328,14 @@ class GradSync:
             for b in range(nb):
                 region = self.q8_region(b)
                 encode(b)
-                self.k.q8_reduce(region, 1, self.q8_plan[b][1], 1, region)
-                decode(b)
+                reduce(region, 1, self.q8_plan[b][1], 1, None, region)
+                decode(b, partials)
             return
 
         def a2a(b):
             m = self.q8_plan[b][1]
             encode(b)
-            return dist.all_to_all_single(self.q_recv[b % 2][:n * m * Q8_SLOT], self.q8_region(b),
+            return dist.all_to_all_single(self.q_recv[b % 2][:n * m * S], self.q8_region(b),
                                           group=self.group, async_op=True)
 
         if nb == 0:
@@ -307,18 +347,16 @@ class GradSync:
                 x[b + 1] = a2a(b + 1)
             x[b].wait()
             m = self.q8_plan[b][1]
-            recv, red = self.q_recv[b % 2][:n * m * Q8_SLOT], self.q_red[b % 2][:m * Q8_SLOT]
-            if self.q_residual_red is not None:
-                self.k.q8_reduce_ef(recv, n, m, n, self.q_residual_red[b], red)
-            else:
-                self.k.q8_reduce(recv, n, m, n, red)
+            recv, red = self.q_recv[b % 2][:n * m * S], self.q_red[b % 2][:m * S]
+            resid = None if self.q_residual_red is None else self.q_residual_red[b]
+            reduce(recv, n, m, n, resid, red)
             ag[b] = dist.all_gather_into_tensor(self.q8_region(b), red, group=self.group,
                                                 async_op=True)
             if b >= 1:
                 ag[b - 1].wait()
-                decode(b - 1)
+                decode(b - 1, partials)
         ag[nb - 1].wait()
-        decode(nb - 1)
+        decode(nb - 1, partials)
 
     def close(self) -> None:
         self.tree.close()

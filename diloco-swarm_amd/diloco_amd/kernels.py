@@ -283,6 +283,19 @@ class HipKernels:
         _lib.call("dl_unpack_avg_q8", tree.handle, bucket, slots.data_ptr(), int(dst_slot),
                   _ptr(partials), _s(slots))
 
+    # the gradient side of the fp4 exchange (dl_fp4_grad.hip). residual None: no error feedback
+    def gather_fp4(self, tree, bucket, src_slot, residual, slots) -> None:
+        """slots <- enc(x), x = the gradients bound to src_slot (+ residual);
+        residual <- x - deq(slots) in place (fp32, the tree's packed layout)."""
+        _lib.call("dl_gather_fp4", tree.handle, bucket, int(src_slot), _ptr(residual),
+                  slots.data_ptr(), _s(slots))
+
+    def unpack_avg_fp4(self, tree, bucket, slots, dst_slot, partials=None) -> None:
+        """dst_slot <- deq of the averaged slots; with partials also the per-chunk Σ of the
+        stored values² (grad_sumsq's, for norm_finish)."""
+        _lib.call("dl_unpack_avg_fp4", tree.handle, bucket, slots.data_ptr(), int(dst_slot),
+                  _ptr(partials), _s(slots))
+
     def unpack_avg(self, tree, bucket, wire, divisor, dst_slot, dst_packed=None) -> None:
         _lib.call("dl_unpack_avg", tree.handle, bucket, wire.data_ptr(), wire_code(wire.dtype),
                   int(divisor), int(dst_slot), _ptr(dst_packed), _s(wire))

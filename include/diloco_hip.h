@@ -502,7 +502,30 @@ DL_API int dl_unpack_avg_q8(dl_tree_t tree, int32_t bucket, const void* slots, i
  * identical to decoding the slots into an fp32 wire and running those on it. The slots are only
  * read; nothing is stored past a chunk's length. 20.53 and 28.53 B/param (24.53 for AdamW
  * without the inner write). slots, outer, the state pointers (and a residual that is given)
- * 16-B aligned. */
+ * 16-B aligned.
+ * The gradient side (the per-step DP gradient average on this wire; dl_fp4_reduce with divisor
+ * n stands between the two). dl_gather_fp4, per chunk c of the bucket, g = slot src_slot
+ * (per-tensor fp32):
+ *   x = g[seg][j]          (residual_packed NULL)
+ *   x = g[seg][j] + r[k]   (r = residual_packed: one rounded fp32 add)
+ *   slot(c) <- enc(x);  r[k] <- x - deq(slot(c))   (in place, by the lane that read it)
+ * byte for byte what dl_delta_fp4 writes for outer = g, inner = +0 (x - (+0) = x bit for bit,
+ * -0 included). Every byte of each slot of the bucket is written, whatever it held before --
+ * scales and nibbles of groups past the chunk's length are zero -- and no byte of any other
+ * slot; of g and r nothing is loaded or stored past a chunk's length (the residual's padding is
+ * never written). Results do not depend on the gradient tensors' alignment, the grid or the
+ * bucket split. 4.53 B/param: 4 read, 0.531 written; with the residual 12.53: 8 read,
+ * 0.531 + 4 written.
+ * dl_unpack_avg_fp4, per chunk c of the bucket, dst = slot dst_slot (per-tensor fp32):
+ *   dst[seg][j] = deq(slot(c))[i]   (the exact power-of-two product above; an E = 255 group
+ *                                    stores NaN)
+ *   partials[c] = Σ of the squares of the values stored to chunk c, when partials is not NULL:
+ *                 fp64, in dl_grad_sumsq's order, bit-identical to dl_grad_sumsq on dst
+ *                 afterwards; written for exactly the bucket's chunk range (n_chunk doubles,
+ *                 8-B aligned)
+ * The slots are only read; nothing is stored past a tensor's length; results do not depend on
+ * alignment, the grid or the bucket split. 4.53 B/param: 0.531 read, 4 written. slots non-null
+ * and 16-B aligned, a given residual 16-B aligned; the slot bound. */
 DL_API int dl_delta_fp4(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
                         const float* outer_packed, float* residual_packed /* NULL: no EF */,
                         void* slots, dl_stream_t stream);
@@ -517,6 +540,11 @@ DL_API int dl_unpack_adamw_fp4(dl_tree_t tree, int32_t bucket, const void* slots
                                float* exp_avg_sq_packed, float decay, float w1, float beta2,
                                float w2, float neg_step_size, float bc2_sqrt, float eps,
                                int32_t inner_slot, dl_stream_t stream);
+DL_API int dl_gather_fp4(dl_tree_t tree, int32_t bucket, int32_t src_slot,
+                         float* residual_packed /* NULL: no EF */, void* slots,
+                         dl_stream_t stream);
+DL_API int dl_unpack_avg_fp4(dl_tree_t tree, int32_t bucket, const void* slots, int32_t dst_slot,
+                             double* partials /* NULL: none */, dl_stream_t stream);
 
 /* ---- serializer (src/serializer.py:11-15) ----------------------------------------------
  * out is fp32 of 2*numel elements: out[0] = meta0, out[1] = meta1, out[numel + i] =
