@@ -519,6 +519,39 @@ DL_API int dl_unpack_sgd(dl_tree_t t, int32_t b, const void* wire, int32_t wire_
   return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_sgd") : hip_fail(e, "dl_unpack_sgd");
 }
 
+// The merging forms' own arguments: a bound inner slot (it is read) and 0 <= alpha < 1
+static int merge_args(dl_tree_t t, int32_t inner_slot, float alpha, const char* who) {
+  if (inner_slot < 0) return fail(DL_E_ARG, "%s: inner_slot %d (the merge reads inner)", who, inner_slot);
+  if (!(alpha >= 0.f && alpha < 1.f))  // NaN and the infinities fail the comparison too
+    return fail(DL_E_ARG, "%s: alpha %g (0 <= alpha < 1)", who, double(alpha));
+  if (inner_slot >= DL_MAX_SLOTS || !t->bound[inner_slot])
+    return fail(DL_E_ARG, "%s: inner_slot %d is not a bound slot", who, inner_slot);
+  return DL_OK;
+}
+
+DL_API int dl_unpack_sgd_merge(dl_tree_t t, int32_t b, const void* wire, int32_t wire_dtype,
+                               int32_t divisor, float* outer, float* mom, float lr, float momentum,
+                               int32_t nesterov, int32_t first_step, int32_t inner_slot,
+                               float alpha, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_sgd_merge", kAutoUnpackSgd));
+  DL_TRY(merge_args(t, inner_slot, alpha, "dl_unpack_sgd_merge"));
+  if (alpha == 0.f)  // inner <- θ: the non-merging instantiation, inner not loaded
+    return dl_unpack_sgd(t, b, wire, wire_dtype, divisor, outer, mom, lr, momentum, nesterov,
+                         first_step, inner_slot, s);
+  DL_TRY(check_packed(wire, "dl_unpack_sgd_merge", "wire"));
+  DL_TRY(check_dtype(wire_dtype, "dl_unpack_sgd_merge"));
+  DL_TRY(check_packed(outer, "dl_unpack_sgd_merge", "outer"));
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_unpack_sgd_merge", mom, lr, momentum, nesterov, first_step, &a));
+  if (divisor < 1) return fail(DL_E_ARG, "dl_unpack_sgd_merge: divisor %d", divisor);
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_sgd_merge"));
+  hipError_t e = dl::launch_unpack_sgd_merge(L, wire, wire_dtype, divisor, outer, mom, a,
+                                             inner_slot, alpha);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_sgd_merge")
+                         : hip_fail(e, "dl_unpack_sgd_merge");
+}
+
 DL_API int dl_delta_sgd(dl_tree_t t, int32_t b, int32_t inner_slot, float* outer, float* mom,
                         float lr, float momentum, int32_t nesterov, int32_t first_step,
                         dl_stream_t s) {
@@ -603,6 +636,31 @@ DL_API int dl_unpack_adamw(dl_tree_t t, int32_t b, const void* wire, int32_t wir
   hipError_t e = dl::launch_unpack_adamw(L, wire, wire_dtype, divisor, outer, exp_avg, exp_avg_sq,
                                          a, inner_slot);
   return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_adamw") : hip_fail(e, "dl_unpack_adamw");
+}
+
+DL_API int dl_unpack_adamw_merge(dl_tree_t t, int32_t b, const void* wire, int32_t wire_dtype,
+                                 int32_t divisor, float* outer, float* exp_avg, float* exp_avg_sq,
+                                 float decay, float w1, float beta2, float w2, float neg_step_size,
+                                 float bc2_sqrt, float eps, int32_t inner_slot, float alpha,
+                                 dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_adamw_merge", kAutoUnpackSgd));
+  DL_TRY(merge_args(t, inner_slot, alpha, "dl_unpack_adamw_merge"));
+  if (alpha == 0.f)  // inner <- θ: the non-merging instantiation, inner not loaded
+    return dl_unpack_adamw(t, b, wire, wire_dtype, divisor, outer, exp_avg, exp_avg_sq, decay, w1,
+                           beta2, w2, neg_step_size, bc2_sqrt, eps, inner_slot, s);
+  DL_TRY(check_packed(wire, "dl_unpack_adamw_merge", "wire"));
+  DL_TRY(check_dtype(wire_dtype, "dl_unpack_adamw_merge"));
+  DL_TRY(check_packed(outer, "dl_unpack_adamw_merge", "outer"));
+  DL_TRY(check_packed(exp_avg, "dl_unpack_adamw_merge", "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, "dl_unpack_adamw_merge", "exp_avg_sq"));
+  if (divisor < 1) return fail(DL_E_ARG, "dl_unpack_adamw_merge: divisor %d", divisor);
+  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_adamw_merge"));
+  hipError_t e = dl::launch_unpack_adamw_merge(L, wire, wire_dtype, divisor, outer, exp_avg,
+                                               exp_avg_sq, a, inner_slot, alpha);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_adamw_merge")
+                         : hip_fail(e, "dl_unpack_adamw_merge");
 }
 
 DL_API int dl_delta_pack_adamw(dl_tree_t t, int32_t b, int32_t inner_slot, float* outer,

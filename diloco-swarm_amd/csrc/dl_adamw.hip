@@ -4,6 +4,8 @@
 // its gradient sources:
 //   dl_unpack_adamw      FromWire, N > 1: reads the summed wire, θ, m, v; writes θ, m, v
 //                        (+ inner): 28 B/param + 4 for the inner write (fp32 wire)
+//   dl_unpack_adamw_merge  the same with the Merge policy: inner is read too and receives
+//                        fmaf(alpha, inner - θ, θ): 36 B/param (20 read, 16 written)
 //   dl_delta_pack_adamw  FromDeltaKeptOnWire, one peer (src/comm.py:118-119: no all-reduce, no
 //                        division): g = θ - inner, the wire written as dl_delta_pack writes it
 //                        and AdamW stepping on the value it holds; 16 B read + 20 B written per
@@ -23,6 +25,15 @@ hipError_t launch_unpack_adamw(const Launch& L, const void* wire, int wire_dtype
                                float* outer, float* m1, float* m2, AdamArgs a, int inner_slot) {
   return with_wire(wire, wire_dtype, divisor, [&](auto grad) {
     return run(L, outer_step(outer, grad, AdamRule{m1, m2, a}, inner_slot));
+  });
+}
+
+// dl_unpack_adamw whose inner write merges (dl_outer_step.h, Merge): five load streams, 36 B/param
+hipError_t launch_unpack_adamw_merge(const Launch& L, const void* wire, int wire_dtype, int divisor,
+                                     float* outer, float* m1, float* m2, AdamArgs a, int inner_slot,
+                                     float alpha) {
+  return with_wire(wire, wire_dtype, divisor, [&](auto grad) {
+    return run(L, outer_step_merge(outer, grad, AdamRule{m1, m2, a}, inner_slot, alpha));
   });
 }
 

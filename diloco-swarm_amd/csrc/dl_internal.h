@@ -78,6 +78,13 @@ hipError_t launch_unpack_avg(const Launch& L, const void* wire, int wire_dtype, 
                              int dst_slot, float* dst_packed);
 hipError_t launch_unpack_sgd(const Launch& L, const void* wire, int wire_dtype, int divisor,
                              float* outer, float* mom, SgdArgs a, int inner_slot);
+// the same steps with the merging inner write: inner <- fmaf(alpha, inner - θ, θ), 0 < alpha < 1
+hipError_t launch_unpack_sgd_merge(const Launch& L, const void* wire, int wire_dtype, int divisor,
+                                   float* outer, float* mom, SgdArgs a, int inner_slot,
+                                   float alpha);
+hipError_t launch_unpack_adamw_merge(const Launch& L, const void* wire, int wire_dtype, int divisor,
+                                     float* outer, float* m1, float* m2, AdamArgs a, int inner_slot,
+                                     float alpha);
 hipError_t launch_delta_sgd(const Launch& L, int inner_slot, float* outer, float* mom, SgdArgs a);
 hipError_t launch_delta_pack_sgd(const Launch& L, int inner_slot, float* outer, void* wire,
                                  int wire_dtype, float* mom, SgdArgs a);

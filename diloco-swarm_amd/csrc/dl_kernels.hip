@@ -11,6 +11,8 @@
 // The outer-step kernels are instantiations of the one body of dl_outer_step.h, gradient
 // source x update rule (the numerics, bit-exact against the reference: beside sgd1, dl_device.h):
 //   dl_unpack_sgd      FromWire x SgdRule             a3 /n + a4 + a5: reads wire, θ, buf
+//   dl_unpack_sgd_merge  the same with the Merge policy: inner is read too and receives
+//                      fmaf(alpha, inner - θ, θ) instead of θ: 28 B/param (24 first step)
 //   dl_shard_sgd       the same body over a flat shard (k_flat, dl_flat.h)
 //   dl_delta_sgd       FromDelta x SgdRule            a2 + a4 + a5 at one peer: 24 B/param (20
 //                      on the first step) instead of 12 + 24 for dl_delta_pack + dl_unpack_sgd
@@ -520,6 +522,19 @@ hipError_t launch_unpack_sgd(const Launch& L, const void* wire, int wire_dtype, 
   return with_wire(wire, wire_dtype, divisor, [&](auto grad) {
     return with_sgd_rule(mom, a, [&](auto rule) {
       return run(L, outer_step(outer, grad, rule, inner_slot));
+    });
+  });
+}
+
+// dl_unpack_sgd whose inner write merges: inner <- fmaf(alpha, inner - θ, θ) (0 < alpha < 1; the
+// caller sends alpha 0 to launch_unpack_sgd). One more load stream, the four of
+// dl_delta_pack_sgd_resume: 28 B/param (fp32 wire; 24 first step, 20 at momentum 0)
+hipError_t launch_unpack_sgd_merge(const Launch& L, const void* wire, int wire_dtype, int divisor,
+                                   float* outer, float* mom, SgdArgs a, int inner_slot,
+                                   float alpha) {
+  return with_wire(wire, wire_dtype, divisor, [&](auto grad) {
+    return with_sgd_rule(mom, a, [&](auto rule) {
+      return run(L, outer_step_merge(outer, grad, rule, inner_slot, alpha));
     });
   });
 }

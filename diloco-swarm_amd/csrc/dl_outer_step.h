@@ -5,8 +5,11 @@
 //         never stored (they are recomputed from the wire that step left);
 //   Rule  what is done with it: SGD (one state stream, the momentum buffer) or AdamW (two,
 //         exp_avg and exp_avg_sq); the arithmetic is sgd1 / adam1 of dl_device.h.
-// and one policy, kDefer: θ and the state are not stored (the wire and inner are), so the step
-// stays pending: the streams as they were plus the wire determine it.
+// and two policies. kDefer: θ and the state are not stored (the wire and inner are), so the step
+// stays pending: the streams as they were plus the wire determine it. Merge (wire sources only):
+// the inner rows are loaded beside the other streams and inner receives fmaf(alpha, x - θ, θ),
+// x the inner value as loaded, instead of θ (Streaming DiLoCo's merge of a model that moved on
+// while the exchange was in flight).
 // Every outer-step kernel of dl_kernels.hip and dl_adamw.hip is an instantiation, so the fused
 // kernels equal the dl_delta_pack + dl_unpack_* pair bit for bit by construction: the element
 // arithmetic is written once, for the float4 rows, the tail lane and the unaligned loop alike.
@@ -105,6 +108,22 @@ struct FromDeltaAfterPending {
   __device__ __forceinline__ float fin(float g) const { return g; }
 };
 
+// ---- the inner write -------------------------------------------------------------------------
+// What inner receives once the rule has produced θ. NoMerge: θ (sync_inner_model). MergeInner:
+// alpha·x + (1 - alpha)·θ as ONE rounded subtract and ONE fma (contract off, like sgd1's), x the
+// inner value loaded before any store. No special case: a non-finite x stays in its own element.
+struct NoMerge {
+  static constexpr bool kOn = false;
+  __device__ __forceinline__ float operator()(float, float th) const { return th; }
+};
+struct MergeInner {
+  static constexpr bool kOn = true;
+  float alpha;
+  __device__ __forceinline__ float operator()(float x, float th) const {
+    return __builtin_fmaf(alpha, x - th, th);
+  }
+};
+
 template <int J>
 __device__ __forceinline__ float& comp(float4& v) {
   if constexpr (J == 0) return v.x;
@@ -128,10 +147,10 @@ struct StateIO<Rule, FromDeltaAfterPending<Pend>> {
 // ---- the body ------------------------------------------------------------------------------
 // Per chunk: every 16-B load up front (gradient stream, θ, states), the subtraction or
 // division, the rule per component, then the stores, one stream's rows back to back: wire, θ,
-// state..., inner (inner_slot -1, wire sources only: no copy-back; kDefer: no θ, no state). The
-// < 4 elements past the last float4 go one per lane; a tensor whose storage is only 4-B aligned
-// goes element-wise.
-template <class Grad, class Rule, bool kDefer = false>
+// state..., inner (inner_slot -1, wire sources only: no copy-back; kDefer: no θ, no state; Merge:
+// the merged rows, computed row by row as they leave). The < 4 elements past the last float4 go
+// one per lane; a tensor whose storage is only 4-B aligned goes element-wise.
+template <class Grad, class Rule, bool kDefer = false, class Merge = NoMerge>
 struct OuterStep {
   static constexpr int K = Rule::kStates;
   static constexpr bool kWireFirst = Grad::kKeepsWire && Rule::kWireFirst;
@@ -139,11 +158,13 @@ struct OuterStep {
   static constexpr bool kStoreState = StateIO<Rule, Grad>::kStore;
   static_assert(!(Grad::kPending && kWireFirst), "a pending step's wire is read before it is stored");
   static_assert(!kDefer || (Grad::kKeepsWire && !Grad::kPending), "a deferred step leaves its wire");
+  static_assert(!Merge::kOn || (!Grad::kDelta && !kDefer), "the merge reads inner beside a wire source");
   using WIO = WireIO<typename Grad::Wire>;
   float* outer;
   Grad grad;
   Rule rule;
   int inner_slot;
+  [[no_unique_address]] Merge merge;  // NoMerge: empty, the kernel arguments are as without it
 
   // component J of row u (a pending source: g holds inner coming in, the gradient going out,
   // old the wire as the pending step left it)
@@ -175,8 +196,9 @@ struct OuterStep {
     for (int k = 0; k < K; ++k) sp[k] = rule.state(k) + ck.poff;
 
     auto one = [&](int i) {
-      float t = th[i], g;
+      float t = th[i], g, xi = 0.f;
       float e[K];
+      if constexpr (Merge::kOn) xi = in[i];
 #pragma unroll
       for (int k = 0; k < K; ++k) e[k] = kLoadState ? sp[k][i] : 0.f;
       if constexpr (Grad::kPending) grad.pend.apply(WIO::ld1(w, i), e, t);
@@ -189,12 +211,12 @@ struct OuterStep {
 #pragma unroll
         for (int k = 0; k < K; ++k) sp[k][i] = e[k];
       }
-      if (copy_back) in[i] = t;
+      if (copy_back) in[i] = merge(xi, t);
     };
 
     if (!copy_back || aligned16(in)) {
       const int nv = ck.len >> 2;
-      float4 x[kUnroll], t[kUnroll], s[K][kUnroll], old[kUnroll];
+      float4 x[kUnroll], t[kUnroll], s[K][kUnroll], old[kUnroll], xi[Merge::kOn ? kUnroll : 1];
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int v = u * kThreads + tid;
@@ -203,6 +225,7 @@ struct OuterStep {
           if constexpr (Grad::kPending) old[u] = WIO::template ld4<NTL>(w, v);
           t[u] = ldf4<NTL>(th, v);
           if constexpr (Grad::kDelta) x[u] = ldf4<NTL>(in, v);
+          if constexpr (Merge::kOn) xi[u] = ldf4<NTL>(in, v);
           if (kLoadState) {
 #pragma unroll
             for (int k = 0; k < K; ++k) s[k][u] = ldf4<NTL>(sp[k], v);
@@ -242,7 +265,17 @@ struct OuterStep {
 #pragma unroll
         for (int k = 0; k < K; ++k) store_rows<NTS>(sp[k], s[k], nv, tid);
       }
-      if (copy_back) store_rows<NTS>(in, t, nv, tid);
+      if constexpr (Merge::kOn) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+          const int v = u * kThreads + tid;
+          if (v < nv)
+            stf4<NTS>(in, v, make_float4(merge(xi[u].x, t[u].x), merge(xi[u].y, t[u].y),
+                                         merge(xi[u].z, t[u].z), merge(xi[u].w, t[u].w)));
+        }
+      } else if (copy_back) {
+        store_rows<NTS>(in, t, nv, tid);
+      }
       const int i = (nv << 2) + tid;
       if (i < ck.len) one(i);
     } else {
@@ -254,6 +287,13 @@ struct OuterStep {
 template <bool kDefer = false, class Grad, class Rule>
 OuterStep<Grad, Rule, kDefer> outer_step(float* outer, Grad grad, Rule rule, int inner_slot) {
   return {outer, grad, rule, inner_slot};
+}
+
+// the step whose inner write merges (inner_slot bound: the caller checked)
+template <class Grad, class Rule>
+OuterStep<Grad, Rule, false, MergeInner> outer_step_merge(float* outer, Grad grad, Rule rule,
+                                                          int inner_slot, float alpha) {
+  return {outer, grad, rule, inner_slot, MergeInner{alpha}};
 }
 
 // ---- host-side dispatch: f is called with the gradient source / rule the arguments select ----

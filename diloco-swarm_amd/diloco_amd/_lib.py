@@ -64,7 +64,11 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
     ),
-    "dl_delta_sgd": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _vp]),
+    "dl_unpack_sgd_merge": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _f32, _vp],
+    ),
+    "dl_delta_sgd": (ctypes.c_int,[_vp, _i32, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _vp]),
     "dl_delta_pack_sgd": (
         ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _f32, _f32, _i32, _i32, _vp],
     ),
@@ -79,6 +83,11 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
          _i32, _vp],
+    ),
+    "dl_unpack_adamw_merge": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
+         _i32, _f32, _vp],
     ),
     "dl_delta_pack_adamw": (
         ctypes.c_int,

@@ -85,6 +85,15 @@ class HipKernels:
                   int(divisor), theta.data_ptr(), _ptr(mom), float(lr), float(momentum),
                   int(nesterov), int(first), int(inner_slot), _s(theta))
 
+    def unpack_sgd_merge(self, tree, bucket, wire, divisor, theta, mom, lr, momentum, nesterov,
+                         first, inner_slot, alpha) -> None:
+        """unpack_sgd whose inner write merges: inner <- fma(alpha, inner - θ, θ), one pass
+        (0 <= alpha < 1; alpha 0 is unpack_sgd; inner_slot must be bound)."""
+        _lib.call("dl_unpack_sgd_merge", tree.handle, bucket, wire.data_ptr(),
+                  wire_code(wire.dtype), int(divisor), theta.data_ptr(), _ptr(mom), float(lr),
+                  float(momentum), int(nesterov), int(first), int(inner_slot), float(alpha),
+                  _s(theta))
+
     def delta_sgd(self, tree, bucket, inner_slot, theta, mom, lr, momentum, nesterov,
                   first) -> None:
         _lib.call("dl_delta_sgd", tree.handle, bucket, inner_slot, theta.data_ptr(), _ptr(mom),
@@ -122,6 +131,13 @@ class HipKernels:
         _lib.call("dl_unpack_adamw", tree.handle, bucket, wire.data_ptr(), wire_code(wire.dtype),
                   int(divisor), theta.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                   *scalars, int(inner_slot), _s(theta))
+
+    def unpack_adamw_merge(self, tree, bucket, wire, divisor, theta, exp_avg, exp_avg_sq, scalars,
+                           inner_slot, alpha) -> None:
+        """unpack_adamw with unpack_sgd_merge's inner write."""
+        _lib.call("dl_unpack_adamw_merge", tree.handle, bucket, wire.data_ptr(),
+                  wire_code(wire.dtype), int(divisor), theta.data_ptr(), exp_avg.data_ptr(),
+                  exp_avg_sq.data_ptr(), *scalars, int(inner_slot), float(alpha), _s(theta))
 
     def delta_pack_adamw(self, tree, bucket, inner_slot, theta, wire, exp_avg, exp_avg_sq,
                          scalars) -> None:

@@ -184,6 +184,28 @@ DL_API int dl_unpack_sgd(dl_tree_t tree, int32_t bucket, const void* wire, int32
                          float momentum, int32_t nesterov, int32_t first_step,
                          int32_t inner_slot, dl_stream_t stream);
 
+/* dl_unpack_sgd whose inner write MERGES instead of overwriting (Streaming DiLoCo, Douillard et
+ * al. 2025: the exchange ran while the inner model moved on, so inner is pulled towards the new
+ * θ rather than replaced by it). dl_unpack_sgd's arguments plus alpha:
+ *   x = inner[seg][j]                     (as loaded, before any store of this launch)
+ *   θ, buf                                exactly dl_unpack_sgd's
+ *   inner[seg][j] = fma(alpha, x - θ, θ)  (x - θ one rounded fp32 subtract, then ONE fma)
+ * i.e. alpha·x + (1 - alpha)·θ. No special case for non-finite values, IEEE rules apply: an Inf or
+ * NaN inner element gives an Inf or NaN there and nowhere else. inner_slot must be a bound slot (below 0, or not bound:
+ * DL_E_ARG); alpha must be finite with 0 <= alpha < 1 (else DL_E_ARG, dl_last_error() names alpha).
+ * alpha == 0 IS dl_unpack_sgd (the same kernel: inner is not loaded, a NaN inner is overwritten).
+ * θ, the momentum and the wire get byte for byte what dl_unpack_sgd gives them; nothing is loaded
+ * or stored past a chunk's length and padding is never written; results do not depend on the
+ * inner tensors' alignment, the grid (dl_tree_tune) or the bucket split. Under DL_TUNE_AUTO the
+ * load / store policy is dl_unpack_sgd's. 28 B/param on the fp32 wire (16 read, 12 written; 24
+ * on the first step, 20 at momentum 0), where dl_unpack_sgd(inner_slot -1) followed by a lerp of
+ * every inner tensor moves 20 + 12. */
+DL_API int dl_unpack_sgd_merge(dl_tree_t tree, int32_t bucket, const void* wire,
+                               int32_t wire_dtype, int32_t divisor, float* outer_packed,
+                               float* mom_packed, float lr, float momentum, int32_t nesterov,
+                               int32_t first_step, int32_t inner_slot, float alpha,
+                               dl_stream_t stream);
+
 /* a2+a4+a5 at ONE peer (src/comm.py:118-119 skips the all-reduce and the division):
  *   g = θ - inner[seg][j]; SGD as dl_unpack_sgd; θ and inner[seg][j] <- new θ
  * One pass, the delta stays in registers: 24 B/param (20 on the first step) instead of 36
@@ -251,6 +273,18 @@ DL_API int dl_unpack_adamw(dl_tree_t tree, int32_t bucket, const void* wire, int
                            float* exp_avg_sq_packed, float decay, float w1, float beta2, float w2,
                            float neg_step_size, float bc2_sqrt, float eps, int32_t inner_slot,
                            dl_stream_t stream);
+
+/* dl_unpack_adamw with dl_unpack_sgd_merge's inner write: θ, exp_avg and exp_avg_sq exactly
+ * dl_unpack_adamw's, then inner[seg][j] = fma(alpha, x - θ, θ), x the inner value as loaded.
+ * dl_unpack_adamw's arguments plus alpha; inner_slot, alpha, alpha == 0, the footprint and the
+ * load / store policy as stated at dl_unpack_sgd_merge. 36 B/param on the fp32 wire (20 read, 16
+ * written). */
+DL_API int dl_unpack_adamw_merge(dl_tree_t tree, int32_t bucket, const void* wire,
+                                 int32_t wire_dtype, int32_t divisor, float* outer_packed,
+                                 float* exp_avg_packed, float* exp_avg_sq_packed, float decay,
+                                 float w1, float beta2, float w2, float neg_step_size,
+                                 float bc2_sqrt, float eps, int32_t inner_slot, float alpha,
+                                 dl_stream_t stream);
 
 /* a2+a3+a4+a5 at ONE peer for an AdamW outer optimizer, keeping the pseudo-gradient:
  *   g = θ - inner[seg][j]; wire[k] = g (bf16 wire: RNE, and AdamW uses the rounded value);
