@@ -98,6 +98,14 @@ OUTER_EXCHANGES = ("sharded", "replicated", "a2a")
 # The device placement keeps "sharded": its reads of .grad / the momentum at N > 1 are
 # collectives, guarded by collective_read() so that a one-rank read raises instead of hanging.
 DEFAULT_EXCHANGE = {"host": "replicated", "device": "sharded"}
+# A gloo DP group (the multi-process tests that share one GPU) stages a device collective
+# through pinned host buffers of its own, the size of the collective, held from the issuing
+# call until the Work is freed. With every bucket of a large tree in flight that is the whole
+# tree in pinned memory per rank, more than a host may allow eight ranks (hipHostMalloc: out of
+# memory). So on such a group the sharded exchange keeps at most this much of the wire in
+# flight: issuing a bucket first waits for the oldest ones beyond it and frees their Work.
+# RCCL reduces in place and keeps every bucket in flight, as before.
+STAGED_INFLIGHT_BYTES = 1 << 30
 
 
 def _none():
@@ -1020,8 +1028,11 @@ class DeviceOuterMirror:
         nb = self.tree.n_buckets
         ags = [None] * nb
         for b in range(nb):
-            if works is not None:
+            if works is not None and works[b] is not None:
                 works[b].wait()
+                # a finished Work is dropped at once (the all_gathers' too): a host-staged
+                # backend holds pinned buffers of the bucket's size in each until it is freed
+                works[b] = None
             lo, hi = self.tree.bucket_ranges[b]
             a, e = self._own(b, n, r)
             if mode == "a2a":
@@ -1032,6 +1043,7 @@ class DeviceOuterMirror:
                                                  group=g, async_op=True)
             if b >= 1:
                 ags[b - 1].wait()
+                ags[b - 1] = None
                 if write:
                     self.k.scatter(self.tree, b - 1, self.d_theta, SLOT_INNER)
         ags[nb - 1].wait()
@@ -1061,8 +1073,11 @@ class DeviceOuterMirror:
         nb = self.tree.n_buckets
         ags = [None] * nb
         for b in range(nb):
-            if works is not None:
+            if works is not None and works[b] is not None:
                 works[b].wait()
+                # a finished Work is dropped at once (the all_gathers' too): a host-staged
+                # backend holds pinned buffers of the bucket's size in each until it is freed
+                works[b] = None
             lo, hi = self.tree.bucket_ranges[b]
             a, e = self._own(b, n, r)
             if mode == "a2a":
@@ -1076,6 +1091,7 @@ class DeviceOuterMirror:
                                                  group=g, async_op=True)
             if b >= 1:
                 ags[b - 1].wait()
+                ags[b - 1] = None
                 if write:
                     self.k.scatter(self.tree, b - 1, self.d_theta, SLOT_INNER)
         ags[nb - 1].wait()
@@ -1110,7 +1126,8 @@ class DeviceOuterMirror:
         """The current stream waits for every collective still in flight on the wire."""
         works, self._works = self._works, None
         for w in works or ():
-            w.wait()
+            if w is not None:
+                w.wait()
 
     def settle_grads(self) -> None:
         """Complete the pending work so the packed .grad holds the reference's values."""
@@ -1271,11 +1288,19 @@ class DeviceOuterMirror:
             ordered_average(self.k, self.tree, self.d_wire, self.d_recv, group, n, rank)
             return
         works = []
+        staged = (4 * self.tree.total > STAGED_INFLIGHT_BYTES
+                  and dist.get_backend(group) == "gloo")
+        oldest = 0  # staged: the first bucket whose collective is still in flight
         for b in range(self.tree.n_buckets):
             if pack is not None:
                 pack(b)
             lo, hi = self.tree.bucket_ranges[b]
             a, e = self._own(b, n, rank)
+            while staged and 4 * (hi - self.tree.bucket_ranges[oldest][0]) > STAGED_INFLIGHT_BYTES \
+                    and oldest < b:
+                works[oldest].wait()
+                works[oldest] = None  # waited for: the optimizer pass skips it
+                oldest += 1
             if mode == "a2a":
                 works.append(dist.all_to_all_single(self.d_recv[lo:hi], self.d_wire[lo:hi],
                                                     group=group, async_op=True))

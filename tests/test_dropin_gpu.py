@@ -249,10 +249,11 @@ def _worker(rank, world, port, mode, out):
             k = default_kernels()
             orig, side, held = k.delta_pack, torch.cuda.Stream(), [False]
 
-            def delta_pack_on_side(*a):
+            # hold_ms: the closure must not read `spin`, which is 0 by the time it runs
+            def delta_pack_on_side(*a, hold_ms=spin):
                 with torch.cuda.stream(side):
                     if not held[0]:
-                        conftest_spin(spin)
+                        conftest_spin(hold_ms)
                         held[0] = True
                     orig(*a)
             k.delta_pack = delta_pack_on_side
