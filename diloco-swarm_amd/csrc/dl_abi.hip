@@ -446,6 +446,14 @@ int check_packed(const void* p, const char* who, const char* what) {
   return DL_OK;
 }
 
+// the top-k wire's entries per slot
+int check_topk_k(int32_t k, const char* who) {
+  if (k < DL_TOPK_MIN_K || k > DL_TOPK_MAX_K || k % 8)
+    return fail(DL_E_ARG, "%s: k %d is not a multiple of 8 in [%d, %d]", who, k, DL_TOPK_MIN_K,
+                DL_TOPK_MAX_K);
+  return DL_OK;
+}
+
 int check_dtype(int32_t d, const char* who) {
   if (d != DL_F32 && d != DL_BF16) return fail(DL_E_ARG, "%s: wire dtype %d", who, d);
   return DL_OK;
@@ -1120,6 +1128,75 @@ DL_API int dl_unpack_adamw_fp4(dl_tree_t t, int32_t b, const void* slots, float*
                                              exp_avg_sq, a, inner_slot);
   return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_adamw_fp4")
                          : hip_fail(e, "dl_unpack_adamw_fp4");
+}
+
+// The top-k wire (dl_topk.hip): the checks, launches and store policies of the fp4 calls, after
+// the check of k.
+DL_API int dl_delta_topk(dl_tree_t t, int32_t b, int32_t inner_slot, const float* outer,
+                         float* residual, int32_t k, void* slots, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_topk_k(k, "dl_delta_topk"));
+  DL_TRY(make_launch(t, b, s, &L, "dl_delta_topk", kAutoDeltaQ8));
+  DL_TRY(check_slot(t, inner_slot, "dl_delta_topk"));
+  DL_TRY(check_packed(outer, "dl_delta_topk", "outer"));
+  if (residual) DL_TRY(check_packed(residual, "dl_delta_topk", "residual"));
+  DL_TRY(check_packed(slots, "dl_delta_topk", "slots"));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_delta_topk"));
+  hipError_t e = dl::launch_delta_topk(L, inner_slot, outer, residual, k, static_cast<uint8_t*>(slots));
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_topk")
+                         : hip_fail(e, "dl_delta_topk");
+}
+
+DL_API int dl_topk_reduce(const void* recv, int32_t n, int32_t m, int32_t divisor, float* residual,
+                          int32_t k, void* out, dl_stream_t s) {
+  DL_TRY(check_topk_k(k, "dl_topk_reduce"));
+  if (n < 1 || m < 0 || divisor < 1)
+    return fail(DL_E_ARG, "dl_topk_reduce: n %d m %d div %d", n, m, divisor);
+  DL_TRY(check_packed(recv, "dl_topk_reduce", "recv"));
+  if (residual) DL_TRY(check_packed(residual, "dl_topk_reduce", "residual"));
+  DL_TRY(check_packed(out, "dl_topk_reduce", "out"));
+  if (recv == out && n != 1) return fail(DL_E_ARG, "dl_topk_reduce: in place needs n_peers == 1");
+  hipError_t e = dl::launch_topk_reduce(static_cast<const uint8_t*>(recv), n, m, divisor, residual,
+                                        k, static_cast<uint8_t*>(out), static_cast<hipStream_t>(s));
+  return e == hipSuccess ? DL_OK : hip_fail(e, "dl_topk_reduce");
+}
+
+DL_API int dl_unpack_sgd_topk(dl_tree_t t, int32_t b, const void* slots, int32_t k, float* outer,
+                              float* mom, float lr, float momentum, int32_t nesterov,
+                              int32_t first_step, int32_t inner_slot, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_topk_k(k, "dl_unpack_sgd_topk"));
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_sgd_topk", kAutoNT));
+  DL_TRY(check_packed(slots, "dl_unpack_sgd_topk", "slots"));
+  DL_TRY(check_packed(outer, "dl_unpack_sgd_topk", "outer"));
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_unpack_sgd_topk", mom, lr, momentum, nesterov, first_step, &a));
+  DL_TRY(check_slot(t, inner_slot, "dl_unpack_sgd_topk", true));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_sgd_topk"));
+  hipError_t e = dl::launch_unpack_sgd_topk(L, static_cast<const uint8_t*>(slots), k, outer, mom, a,
+                                            inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_sgd_topk")
+                         : hip_fail(e, "dl_unpack_sgd_topk");
+}
+
+DL_API int dl_unpack_adamw_topk(dl_tree_t t, int32_t b, const void* slots, int32_t k, float* outer,
+                                float* exp_avg, float* exp_avg_sq, float decay, float w1,
+                                float beta2, float w2, float neg_step_size, float bc2_sqrt,
+                                float eps, int32_t inner_slot, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_topk_k(k, "dl_unpack_adamw_topk"));
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_adamw_topk", kAutoNT));
+  DL_TRY(check_packed(slots, "dl_unpack_adamw_topk", "slots"));
+  DL_TRY(check_packed(outer, "dl_unpack_adamw_topk", "outer"));
+  DL_TRY(check_packed(exp_avg, "dl_unpack_adamw_topk", "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, "dl_unpack_adamw_topk", "exp_avg_sq"));
+  DL_TRY(check_slot(t, inner_slot, "dl_unpack_adamw_topk", true));
+  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_adamw_topk"));
+  hipError_t e = dl::launch_unpack_adamw_topk(L, static_cast<const uint8_t*>(slots), k, outer,
+                                              exp_avg, exp_avg_sq, a, inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_adamw_topk")
+                         : hip_fail(e, "dl_unpack_adamw_topk");
 }
 
 DL_API int dl_gather(dl_tree_t t, int32_t b, int32_t src_slot, void* packed, int32_t dtype,

@@ -22,11 +22,17 @@ ALL_BUCKETS = -1
 MAX_SLOTS = 4
 Q8_SLOT_BYTES = 4160
 FP4_SLOT_BYTES = 2176
+TOPK_MIN_K, TOPK_MAX_K = 8, 256
 IPC_HANDLE_BYTES = 64
 DL_F32, DL_BF16, DL_F16, DL_U8 = 0, 1, 2, 3
 TUNE_NT_LOADS, TUNE_NT_STORES, TUNE_WT_STORES, TUNE_PAIRS = 1, 2, 8, 16
 TUNE_AUTO = -1
 COPY_WIDE, COPY_READ, COPY_WRITE = 8, 16, 32
+
+
+def TOPK_SLOT_BYTES(k: int) -> int:
+    """DL_TOPK_SLOT_BYTES(k): k fp32 values, then k u16 indices."""
+    return 6 * k
 
 
 def COPY_STREAMS(s: int) -> int:
@@ -137,6 +143,16 @@ SIGNATURES = {
     "dl_unpack_adamw_fp4": (
         ctypes.c_int,
         [_vp, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp],
+    ),
+    "dl_delta_topk": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "dl_topk_reduce": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "dl_unpack_sgd_topk": (
+        ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
+    ),
+    "dl_unpack_adamw_topk": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32,
+         _vp],
     ),
     "dl_gather_q8": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "dl_gather_q8_ef": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),

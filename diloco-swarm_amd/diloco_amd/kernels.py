@@ -282,6 +282,32 @@ class HipKernels:
                   exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars, int(inner_slot),
                   _s(theta))
 
+    # top-k sparse wire codec (DL_TOPK_SLOT_BYTES(k) = 6k-byte slots, one per chunk; dl_topk.hip).
+    # residual None: no error feedback
+    def delta_topk(self, tree, bucket, inner_slot, theta, residual, k, slots) -> None:
+        """slots <- the k largest-magnitude entries of x per chunk, x = θ - inner (+ residual);
+        residual <- x with +0 at the selected positions, in place."""
+        _lib.call("dl_delta_topk", tree.handle, bucket, inner_slot, theta.data_ptr(),
+                  _ptr(residual), int(k), slots.data_ptr(), _s(theta))
+
+    def topk_reduce(self, recv, n_peers, n_slots, divisor, residual, k, out) -> None:
+        """out <- select_k((Σ_r decode(recv[r])) / divisor (+ residual)), r in rank order;
+        residual (the owner's n_slots * CHUNK_ELEMS floats) rewritten in place."""
+        _lib.call("dl_topk_reduce", recv.data_ptr(), int(n_peers), int(n_slots), int(divisor),
+                  _ptr(residual), int(k), out.data_ptr(), _s(out))
+
+    def unpack_sgd_topk(self, tree, bucket, slots, k, theta, mom, lr, momentum, nesterov, first,
+                        inner_slot) -> None:
+        _lib.call("dl_unpack_sgd_topk", tree.handle, bucket, slots.data_ptr(), int(k),
+                  theta.data_ptr(), _ptr(mom), float(lr), float(momentum), int(nesterov),
+                  int(first), int(inner_slot), _s(theta))
+
+    def unpack_adamw_topk(self, tree, bucket, slots, k, theta, exp_avg, exp_avg_sq, scalars,
+                          inner_slot) -> None:
+        _lib.call("dl_unpack_adamw_topk", tree.handle, bucket, slots.data_ptr(), int(k),
+                  theta.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars,
+                  int(inner_slot), _s(theta))
+
     # the gradient side of the int8 exchange (dl_q8_grad.hip)
     def gather_q8(self, tree, bucket, src_slot, slots) -> None:
         """slots <- quantise(the gradients bound to src_slot), one slot per chunk."""

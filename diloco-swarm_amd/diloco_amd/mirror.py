@@ -69,6 +69,18 @@ def _decode_fp4(sl: torch.Tensor) -> torch.Tensor:
     return bits.view(torch.float32)
 
 
+def _decode_topk(sl: torch.Tensor, k: int) -> torch.Tensor:
+    """[nch, 6k] top-k slots -> [nch, 4096] fp32: +0 with value[e] at index[e] (the dense chunk
+    dl_unpack_*_topk build in LDS). The values move as int32, so every bit pattern survives."""
+    nch = sl.shape[0]
+    val = sl[:, :4 * k].contiguous().view(torch.int32)
+    idx = sl[:, 4 * k:].contiguous().view(torch.int16).to(torch.int64) & (S_CHUNK - 1)
+    out = torch.zeros(nch, S_CHUNK, dtype=torch.int32, device=sl.device)
+    # entries in order, so an all-zero slot (k entries at index 0, all +0) decodes to zeros
+    out.scatter_(1, idx, val)
+    return out.view(torch.float32)
+
+
 def _check_host_params(params: Sequence[torch.Tensor]) -> None:
     for i, p in enumerate(params):
         if p.device.type != "cpu":
@@ -79,11 +91,13 @@ def _check_host_params(params: Sequence[torch.Tensor]) -> None:
 
 
 WRITE_BACKS = ("lazy", "sync", "deferred")
-OUTER_WIRES = ("f32", "bf16", "int8", "fp4")
+OUTER_WIRES = ("f32", "bf16", "int8", "fp4", "topk")
 # The wires that send one fixed-size slot per tree chunk (q8_slot_plan; _all_reduce_q8): "int8"
-# (dl_q8.hip) and "fp4" (dl_fp4.hip, OCP MX block-scaled E2M1). They share the slot plan, the
-# exchange, its buffers and pipelining, and the residual arenas of error feedback.
-SLOT_WIRES = ("int8", "fp4")
+# (dl_q8.hip), "fp4" (dl_fp4.hip, OCP MX block-scaled E2M1) and "topk" (dl_topk.hip: the k
+# largest-magnitude entries of a chunk, 6k bytes). They share the slot plan, the exchange, its
+# buffers and pipelining, and the residual arenas of error feedback.
+SLOT_WIRES = ("int8", "fp4", "topk")
+DEFAULT_TOPK = 64  # entries per chunk of the "topk" wire (DILOCO_OUTER_TOPK)
 # The DP exchange behind sync_gradients for the device outer model at N > 1:
 #   "sharded"     per bucket RCCL reduce_scatter -> Nesterov SGD on this rank's 1/n of θ and
 #                 the momentum -> RCCL all_gather of θ (20 + 20/n B/param of HBM)
@@ -680,7 +694,7 @@ class DeviceOuterMirror:
     def __init__(self, outer_model: torch.nn.Module, device: torch.device, kernels=None,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = False,
                  wire: str = "f32", exchange: str = "sharded", keep_params: bool = False,
-                 error_feedback: bool = False):
+                 error_feedback: bool = False, topk: int = DEFAULT_TOPK):
         """keep_params: the outer model's Parameter objects stay the ones it has (their class
         switched to OuterParameter in place) -- for an outer model that got its device only
         at its first compute_pseudo_gradient, after get_optimizer took references to them.
@@ -698,6 +712,10 @@ class DeviceOuterMirror:
         # a residual) and the re-quantised average the owner's (dl_q8_reduce_ef; dl_fp4_reduce
         # with one); the arenas, of one shape for both wires, are made at the first exchange
         self.error_feedback = bool(error_feedback)
+        self.topk = int(topk)  # entries per chunk; the "topk" wire only
+        if wire == "topk" and (self.topk % 8 or not _lib.TOPK_MIN_K <= self.topk <= _lib.TOPK_MAX_K):
+            raise ValueError(f"topk {topk}: a multiple of 8 in [{_lib.TOPK_MIN_K}, "
+                             f"{_lib.TOPK_MAX_K}]")
         self._q8_res: Optional[torch.Tensor] = None
         self._q8_res_load: Optional[list] = None  # a loaded stage-2 state, until the buffers exist
         self.exchange = exchange
@@ -1317,7 +1335,9 @@ class DeviceOuterMirror:
     # four places: the slot size (_q8_buffers), the two lossy kernels (_slot_encode,
     # _slot_reduce), the fused optimizer passes (_q8_sgd, _q8_adamw) and .grad's decode.
     def _slot_encode(self, b: int, slot: int, theta, residual, region) -> None:
-        if self.wire == "fp4":
+        if self.wire == "topk":
+            self.k.delta_topk(self.tree, b, slot, theta, residual, self.topk, region)
+        elif self.wire == "fp4":
             self.k.delta_fp4(self.tree, b, slot, theta, residual, region)
         elif residual is not None:
             self.k.delta_q8_ef(self.tree, b, slot, theta, residual, region)
@@ -1325,7 +1345,9 @@ class DeviceOuterMirror:
             self.k.delta_q8(self.tree, b, slot, theta, region)
 
     def _slot_reduce(self, recv, n: int, m: int, residual, red) -> None:
-        if self.wire == "fp4":
+        if self.wire == "topk":
+            self.k.topk_reduce(recv, n, m, n, residual, self.topk, red)
+        elif self.wire == "fp4":
             self.k.fp4_reduce(recv, n, m, n, residual, red)
         elif residual is not None:
             self.k.q8_reduce_ef(recv, n, m, n, residual, red)
@@ -1344,6 +1366,8 @@ class DeviceOuterMirror:
         from .kernels import FP4_SLOT, Q8_SLOT
 
         S = FP4_SLOT if self.wire == "fp4" else Q8_SLOT  # the slot size is the codec's
+        if self.wire == "topk":
+            S = _lib.TOPK_SLOT_BYTES(self.topk)
         plan, base, rbase, mmax = q8_slot_plan(self.tree.bucket_chunks, n)
         z = dict(dtype=torch.uint8, device=self.device)
         segs = []
@@ -1493,7 +1517,9 @@ class DeviceOuterMirror:
         for b in range(self.tree.n_buckets):
             nch, m, base, _ = q["plan"][b]
             sl = q["slots"][base * S:(base + nch) * S].view(nch, S)
-            if self.wire == "fp4":
+            if self.wire == "topk":
+                g = _decode_topk(sl, self.topk)
+            elif self.wire == "fp4":
                 g = _decode_fp4(sl)
             else:
                 g = sl[:, S - C:].contiguous().view(torch.int8).float() * \
@@ -1516,6 +1542,11 @@ class DeviceOuterMirror:
         for b in range(self.tree.n_buckets):
             if works is not None:
                 works[b].wait()
+            if self.wire == "topk":
+                self.k.unpack_sgd_topk(self.tree, b, self._q8_region(q, b), self.topk,
+                                       self.d_theta, mom, lr, momentum, nesterov, first,
+                                       SLOT_INNER if write else -1)
+                continue
             step = self.k.unpack_sgd_fp4 if self.wire == "fp4" else self.k.unpack_sgd_q8
             step(self.tree, b, self._q8_region(q, b), self.d_theta, mom, lr, momentum, nesterov,
                  first, SLOT_INNER if write else -1)
@@ -1533,6 +1564,11 @@ class DeviceOuterMirror:
         for b in range(self.tree.n_buckets):
             if works is not None:
                 works[b].wait()
+            if self.wire == "topk":
+                self.k.unpack_adamw_topk(self.tree, b, self._q8_region(q, b), self.topk,
+                                         self.d_theta, self.d_m1, self.d_m2, scalars,
+                                         SLOT_INNER if write else -1)
+                continue
             step = self.k.unpack_adamw_fp4 if self.wire == "fp4" else self.k.unpack_adamw_q8
             step(self.tree, b, self._q8_region(q, b), self.d_theta, self.d_m1, self.d_m2, scalars,
                  SLOT_INNER if write else -1)
@@ -1958,7 +1994,7 @@ class LazyHostOuterMirror:
     def __init__(self, outer_model: torch.nn.Module, device: torch.device, kernels=None,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = True,
                  wire: str = "f32", exchange: str = DEFAULT_EXCHANGE["host"],
-                 error_feedback: bool = False):
+                 error_feedback: bool = False, topk: int = DEFAULT_TOPK):
         self.device = torch.device(device)
         params = module_params(outer_model)
         if not params:
@@ -1970,7 +2006,7 @@ class LazyHostOuterMirror:
                 torch.nn.Parameter(_DATA.__get__(p).to(self.device), p.requires_grad)
                 for p in params])
         self.dev = DeviceOuterMirror(twin, self.device, kernels, bucket_cap_elems, fused, wire,
-                                     exchange, error_feedback=error_feedback)
+                                     exchange, error_feedback=error_feedback, topk=topk)
         self._twin = twin
         self.fused, self.wire, self.exchange = fused, wire, exchange
         from .utils import env_flag

@@ -81,9 +81,10 @@ import torch.nn as nn
 from torch.optim import SGD, AdamW, Optimizer
 
 from .kernels import default_kernels
-from .mirror import (DEFAULT_EXCHANGE, OUTER_EXCHANGES, OUTER_WIRES, SLOT_WIRES, WRITE_BACKS,
-                     DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
+from .mirror import (DEFAULT_EXCHANGE, DEFAULT_TOPK, OUTER_EXCHANGES, OUTER_WIRES, SLOT_WIRES,
+                     WRITE_BACKS, DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
 from .optim import InnerAdamW, OuterAdamW, OuterSGD
+from . import _lib
 from ._lib import ALL_BUCKETS
 from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_GRAD
 
@@ -96,6 +97,7 @@ _WIRE = "_diloco_wire"
 _EXCHANGE = "_diloco_exchange"
 _EXCHANGE_ASKED = "_diloco_exchange_asked"  # by argument or DILOCO_OUTER_EXCHANGE
 _Q8_EF = "_diloco_q8_ef"  # int8 wire with error feedback (DILOCO_OUTER_Q8_EF)
+_TOPK = "_diloco_topk"  # entries per chunk of the "topk" wire (DILOCO_OUTER_TOPK)
 _ADAMW = "_diloco_adamw"  # an optim.OuterAdamW is attached
 OUTER_ADAMW = ("torch", "fused")
 INNER_ADAMW = ("torch", "fused")  # DILOCO_INNER_ADAMW: the inner optimizer's step
@@ -158,6 +160,8 @@ def outer_mirror(outer_model: nn.Module, device=None):
         k = default_kernels()
         # the int8 wire's error feedback is named only where it is on (off: the call as before)
         ef = {"error_feedback": True} if getattr(outer_model, _Q8_EF, False) else {}
+        if getattr(outer_model, _WIRE, "f32") == "topk":  # likewise named for its own wire only
+            ef["topk"] = getattr(outer_model, _TOPK)
         if getattr(outer_model, _PLACEMENT, "host") == "device":
             p = next(outer_model.parameters(), None)
             if p is None:
@@ -213,7 +217,8 @@ def _inner_device(inner_model: nn.Module) -> torch.device:
 
 def get_outer_model(inner_model: nn.Module, placement: str = None,
                     write_back: str = None, fused: bool = None, wire: str = None,
-                    exchange: str = None, error_feedback: bool = None) -> nn.Module:
+                    exchange: str = None, error_feedback: bool = None,
+                    topk: int = None) -> nn.Module:
     """Initializes the outer model from the inner model (src/utils.py:213-216).
 
     placement "host" (the reference's, default) or "device" (in HBM: on the inner model's GPU;
@@ -228,7 +233,12 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     (dl_delta_q8_ef, dl_q8_reduce_ef); q8_error_feedback_state / load_q8_error_feedback_state
     let a checkpoint carry the residuals. The fp4 wire takes error_feedback too (None reads
     DILOCO_OUTER_FP4_EF, default off): dl_delta_fp4 and dl_fp4_reduce with their residuals, the
-    same arenas and the same two state helpers."""
+    same arenas and the same two state helpers. wire="topk" sends the k = topk (None reads
+    DILOCO_OUTER_TOPK, default 64; a multiple of 8 in [8, 256]) largest-magnitude entries of
+    every 4096-element chunk as exact fp32 values (dl_delta_topk, dl_topk_reduce,
+    dl_unpack_sgd_topk / dl_unpack_adamw_topk); its error_feedback (None reads
+    DILOCO_OUTER_TOPK_EF) is ON by default, for this wire only -- without it whatever was not
+    selected is lost -- and error_feedback=False is allowed."""
     if placement is None:
         placement = os.environ.get("DILOCO_OUTER_PLACEMENT", "host")
     if placement not in PLACEMENTS:
@@ -245,10 +255,19 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
         raise ValueError(f"wire {wire!r}: one of {OUTER_WIRES}")
     if error_feedback is None:  # each variable is consulted for its own wire only
         error_feedback = ((wire == "int8" and env_flag("DILOCO_OUTER_Q8_EF", False))
-                          or (wire == "fp4" and env_flag("DILOCO_OUTER_FP4_EF", False)))
+                          or (wire == "fp4" and env_flag("DILOCO_OUTER_FP4_EF", False))
+                          or (wire == "topk" and env_flag("DILOCO_OUTER_TOPK_EF", True)))
     elif error_feedback and wire not in SLOT_WIRES:
         raise ValueError(f"error_feedback=True compensates the int8 / fp4 wire's quantiser; the "
                          f"wire is {wire!r}")
+    if wire == "topk":
+        if topk is None:
+            topk = int(os.environ.get("DILOCO_OUTER_TOPK") or DEFAULT_TOPK)
+        if topk % 8 or not _lib.TOPK_MIN_K <= topk <= _lib.TOPK_MAX_K:
+            raise ValueError(f"topk {topk}: a multiple of 8 in [{_lib.TOPK_MIN_K}, "
+                             f"{_lib.TOPK_MAX_K}]")
+    elif topk is not None:
+        raise ValueError(f"topk={topk} is the 'topk' wire's entries per chunk; the wire is {wire!r}")
     if exchange is None:
         exchange = os.environ.get("DILOCO_OUTER_EXCHANGE") or None
     asked = exchange is not None
@@ -283,6 +302,7 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     object.__setattr__(outer_model, _FUSED, bool(fused) and lazy)
     object.__setattr__(outer_model, _WIRE, wire)
     object.__setattr__(outer_model, _Q8_EF, bool(error_feedback))
+    object.__setattr__(outer_model, _TOPK, topk)
     object.__setattr__(outer_model, _EXCHANGE, exchange)
     object.__setattr__(outer_model, _EXCHANGE_ASKED, asked)
     if placement == "device" and has_params and not getattr(outer_model, _PENDING, False):

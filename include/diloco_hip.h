@@ -37,6 +37,10 @@ extern "C" {
 #define DL_MAX_SLOTS 4         /* per-tensor pointer tables per tree */
 #define DL_Q8_SLOT_BYTES 4160  /* int8 wire: 64-B header (fp32 scale) + DL_CHUNK_ELEMS int8 */
 #define DL_FP4_SLOT_BYTES 2176 /* fp4 wire: DL_CHUNK_ELEMS/32 scale bytes + DL_CHUNK_ELEMS/2 */
+/* top-k wire: k entries per chunk, k a multiple of 8; k fp32 values, then k u16 indices */
+#define DL_TOPK_MIN_K 8
+#define DL_TOPK_MAX_K 256
+#define DL_TOPK_SLOT_BYTES(k) (6 * (k))
 
 /* wire / packed dtypes */
 #define DL_F32 0
@@ -579,6 +583,71 @@ DL_API int dl_gather_fp4(dl_tree_t tree, int32_t bucket, int32_t src_slot,
                          dl_stream_t stream);
 DL_API int dl_unpack_avg_fp4(dl_tree_t tree, int32_t bucket, const void* slots, int32_t dst_slot,
                              double* partials /* NULL: none */, dl_stream_t stream);
+
+/* ---- top-k sparse wire codec (not in the reference) ----------------------------------------
+ * The pseudo-gradient exchange of the int8 / fp4 wires with a sparse slot: the k entries of
+ * largest magnitude of each chunk, exact fp32 values, on the same slot plan, collectives and
+ * residual arenas. k is a run-time argument, a multiple of 8 with DL_TOPK_MIN_K <= k <=
+ * DL_TOPK_MAX_K; anything else is DL_E_ARG and dl_last_error() names k. One
+ * DL_TOPK_SLOT_BYTES(k) = 6k-byte slot per chunk of the bucket, in chunk order (a multiple of
+ * 48 B, so consecutive slots keep 16-B alignment):
+ *   bytes [0, 4k)   k fp32 values
+ *   bytes [4k, 6k)  k u16 indices into the chunk; entry e pairs value e with index e
+ * 6k/4096 B/param: 0.094 at k = 64.
+ * A chunk has DL_CHUNK_ELEMS positions; positions at or past the chunk's length hold +0.
+ *   key(x) = bits(x) & 0x7fffffff as an unsigned integer: monotone in |x|; a NaN outranks Inf,
+ *   Inf outranks every finite value.
+ *   Position i ranks before position j iff key_i > key_j, or key_i == key_j and i < j.
+ * select_k(x): the slot carries the first k positions in that order, stored in ascending index
+ * order; each value is the element's own 32 bits (-0, denormals and NaN payloads included).
+ * There are always exactly k entries with strictly ascending indices: when fewer than k
+ * elements are non-zero, zeros are selected by the same rule, lowest index first, so positions
+ * past the length are taken last.
+ * Decode: a dense chunk of +0 with value[e] at index[e]. A slot of all zero bytes is valid too
+ * and decodes to zeros (the never-owned padding slots of a buffer start like that; the reduce
+ * of zero slots writes indices 0..k-1 with +0 values, which also decodes to zeros).
+ * Residual, where given: r[i] <- +0 if position i was selected (a plain store), r[i] <- x_i
+ * otherwise. No arithmetic: a selected NaN or Inf leaves a clean residual; an unselected one
+ * (more than k non-finite elements in a chunk) stays in the residual, IEEE rules, no special
+ * case.
+ * dl_delta_topk, per chunk c of the bucket and element j of the packed space:
+ *   x = outer[j] - inner[seg][i]           (residual_packed NULL)
+ *   x = (outer[j] - inner[seg][i]) + r[j]  (two rounded fp32 operations, as dl_delta_fp4)
+ *   slot(c) <- select_k(x); r as above, in place, by the lane that read it
+ * Every byte of every launched slot is written and no byte of any other slot; nothing of θ,
+ * inner or r is touched past a chunk's length; results do not depend on the inner tensors'
+ * alignment, the grid or the bucket split. 8 + 6k/4096 B/param (16 + 6k/4096 with the
+ * residual: 16.09 at k = 64).
+ * dl_topk_reduce, on the owner of n_slots slots (recv laid out [peer][slot]), per owned slot:
+ *   acc[i] = +0; for peers in rank order, for each entry: acc[index] = acc[index] + value
+ *   (one rounded add per entry); if divisor > 1: acc /= divisor (IEEE division);
+ *   x = acc (+ r2[slot*DL_CHUNK_ELEMS + i], residual not NULL);
+ *   out slot <- select_k(x) over all DL_CHUNK_ELEMS positions; r2 as above
+ * out may alias recv only at n_peers == 1. Every peer receives byte-identical averaged slots.
+ * An index is taken modulo DL_CHUNK_ELEMS; a slot whose indices repeat (other than the
+ * all-zero slot) is not a valid slot.
+ * dl_unpack_sgd_topk / dl_unpack_adamw_topk: g = decode(slot), then one element of
+ * dl_unpack_sgd / dl_unpack_adamw (divisor 1) and inner[seg][i] = θ (inner_slot < 0: no inner
+ * write): bit-identical to decoding the slots into an fp32 wire and running those on it. Every
+ * element inside the chunk is stepped (a zero gradient still decays momentum); the slots are
+ * only read; nothing is stored past a chunk's length. 20 + 6k/4096 and 28 + 6k/4096 B/param
+ * (24 + 6k/4096 for AdamW without the inner write). slots, outer, the state pointers (and a
+ * residual that is given) 16-B aligned; the argument checks are the fp4 entry points'. */
+DL_API int dl_delta_topk(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
+                         const float* outer_packed, float* residual_packed /* NULL: none */,
+                         int32_t k, void* slots, dl_stream_t stream);
+DL_API int dl_topk_reduce(const void* recv, int32_t n_peers, int32_t n_slots, int32_t divisor,
+                          float* residual /* NULL: none */, int32_t k, void* out,
+                          dl_stream_t stream);
+DL_API int dl_unpack_sgd_topk(dl_tree_t tree, int32_t bucket, const void* slots, int32_t k,
+                              float* outer_packed, float* mom_packed, float lr, float momentum,
+                              int32_t nesterov, int32_t first_step, int32_t inner_slot,
+                              dl_stream_t stream);
+DL_API int dl_unpack_adamw_topk(dl_tree_t tree, int32_t bucket, const void* slots, int32_t k,
+                                float* outer_packed, float* exp_avg_packed,
+                                float* exp_avg_sq_packed, float decay, float w1, float beta2,
+                                float w2, float neg_step_size, float bc2_sqrt, float eps,
+                                int32_t inner_slot, dl_stream_t stream);
 
 /* ---- serializer (src/serializer.py:11-15) ----------------------------------------------
  * out is fp32 of 2*numel elements: out[0] = meta0, out[1] = meta1, out[numel + i] =
