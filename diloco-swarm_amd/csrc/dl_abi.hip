@@ -1130,6 +1130,70 @@ DL_API int dl_unpack_adamw_fp4(dl_tree_t t, int32_t b, const void* slots, float*
                          : hip_fail(e, "dl_unpack_adamw_fp4");
 }
 
+// The rotated fp4 wire (dl_fp4_rot.hip): the checks, launches and store policies of the fp4 calls
+// above; any seed is valid.
+DL_API int dl_delta_fp4_rot(dl_tree_t t, int32_t b, int32_t inner_slot, const float* outer,
+                            float* residual, uint32_t seed, void* slots, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_delta_fp4_rot", kAutoDeltaQ8));
+  DL_TRY(check_slot(t, inner_slot, "dl_delta_fp4_rot"));
+  DL_TRY(check_packed(outer, "dl_delta_fp4_rot", "outer"));
+  if (residual) DL_TRY(check_packed(residual, "dl_delta_fp4_rot", "residual"));
+  DL_TRY(check_packed(slots, "dl_delta_fp4_rot", "slots"));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_delta_fp4_rot"));
+  hipError_t e = dl::launch_delta_fp4_rot(L, inner_slot, outer, residual, seed,
+                                          static_cast<uint8_t*>(slots));
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_fp4_rot")
+                         : hip_fail(e, "dl_delta_fp4_rot");
+}
+
+DL_API int dl_unpack_sgd_fp4_rot(dl_tree_t t, int32_t b, const void* slots, uint32_t seed,
+                                 float* outer, float* mom, float lr, float momentum,
+                                 int32_t nesterov, int32_t first_step, int32_t inner_slot,
+                                 dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_sgd_fp4_rot", kAutoNT));
+  DL_TRY(check_packed(slots, "dl_unpack_sgd_fp4_rot", "slots"));
+  DL_TRY(check_packed(outer, "dl_unpack_sgd_fp4_rot", "outer"));
+  dl::SgdArgs a;
+  DL_TRY(sgd_args("dl_unpack_sgd_fp4_rot", mom, lr, momentum, nesterov, first_step, &a));
+  DL_TRY(check_slot(t, inner_slot, "dl_unpack_sgd_fp4_rot", true));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_sgd_fp4_rot"));
+  hipError_t e = dl::launch_unpack_sgd_fp4_rot(L, static_cast<const uint8_t*>(slots), seed, outer,
+                                               mom, a, inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_sgd_fp4_rot")
+                         : hip_fail(e, "dl_unpack_sgd_fp4_rot");
+}
+
+DL_API int dl_unpack_adamw_fp4_rot(dl_tree_t t, int32_t b, const void* slots, uint32_t seed,
+                                   float* outer, float* exp_avg, float* exp_avg_sq, float decay,
+                                   float w1, float beta2, float w2, float neg_step_size,
+                                   float bc2_sqrt, float eps, int32_t inner_slot, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_adamw_fp4_rot", kAutoNT));
+  DL_TRY(check_packed(slots, "dl_unpack_adamw_fp4_rot", "slots"));
+  DL_TRY(check_packed(outer, "dl_unpack_adamw_fp4_rot", "outer"));
+  DL_TRY(check_packed(exp_avg, "dl_unpack_adamw_fp4_rot", "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, "dl_unpack_adamw_fp4_rot", "exp_avg_sq"));
+  DL_TRY(check_slot(t, inner_slot, "dl_unpack_adamw_fp4_rot", true));
+  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
+  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_adamw_fp4_rot"));
+  hipError_t e = dl::launch_unpack_adamw_fp4_rot(L, static_cast<const uint8_t*>(slots), seed, outer,
+                                                 exp_avg, exp_avg_sq, a, inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_adamw_fp4_rot")
+                         : hip_fail(e, "dl_unpack_adamw_fp4_rot");
+}
+
+DL_API int dl_decode_fp4_rot(dl_tree_t t, int32_t b, const void* slots, uint32_t seed,
+                             float* dst, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_packed(slots, "dl_decode_fp4_rot", "slots"));
+  DL_TRY(check_packed(dst, "dl_decode_fp4_rot", "dst"));
+  DL_TRY(make_launch(t, b, s, &L, "dl_decode_fp4_rot", kAutoNT));
+  hipError_t e = dl::launch_decode_fp4_rot(L, static_cast<const uint8_t*>(slots), seed, dst);
+  return e == hipSuccess ? DL_OK : hip_fail(e, "dl_decode_fp4_rot");
+}
+
 // The top-k wire (dl_topk.hip): the checks, launches and store policies of the fp4 calls, after
 // the check of k.
 DL_API int dl_delta_topk(dl_tree_t t, int32_t b, int32_t inner_slot, const float* outer,

@@ -125,6 +125,16 @@ hipError_t launch_unpack_sgd_fp4(const Launch& L, const uint8_t* slots, float* o
                                  SgdArgs a, int inner_slot);
 hipError_t launch_unpack_adamw_fp4(const Launch& L, const uint8_t* slots, float* outer, float* m1,
                                    float* m2, AdamArgs a, int inner_slot);
+// the fp4 wire behind the randomised Hadamard rotation of `seed` (dl_fp4_rot.hip); launch_fp4_reduce
+// serves it unchanged. launch_decode_fp4_rot: dst (packed) <- the values the steps form
+hipError_t launch_delta_fp4_rot(const Launch& L, int inner_slot, const float* outer, float* resid,
+                                uint32_t seed, uint8_t* slots);
+hipError_t launch_unpack_sgd_fp4_rot(const Launch& L, const uint8_t* slots, uint32_t seed,
+                                     float* outer, float* mom, SgdArgs a, int inner_slot);
+hipError_t launch_unpack_adamw_fp4_rot(const Launch& L, const uint8_t* slots, uint32_t seed,
+                                       float* outer, float* m1, float* m2, AdamArgs a,
+                                       int inner_slot);
+hipError_t launch_decode_fp4_rot(const Launch& L, const uint8_t* slots, uint32_t seed, float* dst);
 // the top-k sparse wire of the pseudo-gradient exchange (dl_topk.hip): k entries per 6k-byte slot
 // (the caller checked k). resid as for the fp4 wire
 hipError_t launch_delta_topk(const Launch& L, int inner_slot, const float* outer, float* resid,

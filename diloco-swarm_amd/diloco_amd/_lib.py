@@ -41,6 +41,7 @@ def COPY_STREAMS(s: int) -> int:
 
 
 _i32, _i64, _u64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
+_u32 = ctypes.c_uint32
 _vp = ctypes.c_void_p
 _pi64 = ctypes.POINTER(ctypes.c_int64)
 _pi32 = ctypes.POINTER(ctypes.c_int32)
@@ -144,6 +145,16 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp],
     ),
+    "dl_delta_fp4_rot": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _u32, _vp, _vp]),
+    "dl_unpack_sgd_fp4_rot": (
+        ctypes.c_int, [_vp, _i32, _vp, _u32, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
+    ),
+    "dl_unpack_adamw_fp4_rot": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _u32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32,
+         _vp],
+    ),
+    "dl_decode_fp4_rot": (ctypes.c_int, [_vp, _i32, _vp, _u32, _vp, _vp]),
     "dl_delta_topk": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "dl_topk_reduce": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "dl_unpack_sgd_topk": (

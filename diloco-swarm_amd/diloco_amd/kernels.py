@@ -282,6 +282,31 @@ class HipKernels:
                   exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars, int(inner_slot),
                   _s(theta))
 
+    # the fp4 wire behind the randomised Hadamard rotation of `seed` (dl_fp4_rot.hip): the slot
+    # format and fp4_reduce are the plain wire's; the seed must be the same on every rank
+    def delta_fp4_rot(self, tree, bucket, inner_slot, theta, residual, seed, slots) -> None:
+        """slots <- enc(R(x)), x = θ - inner (+ residual); residual <- x - R⁻¹(deq(slots)) in
+        place, in the original domain."""
+        _lib.call("dl_delta_fp4_rot", tree.handle, bucket, inner_slot, theta.data_ptr(),
+                  _ptr(residual), int(seed), slots.data_ptr(), _s(theta))
+
+    def unpack_sgd_fp4_rot(self, tree, bucket, slots, seed, theta, mom, lr, momentum, nesterov,
+                           first, inner_slot) -> None:
+        _lib.call("dl_unpack_sgd_fp4_rot", tree.handle, bucket, slots.data_ptr(), int(seed),
+                  theta.data_ptr(), _ptr(mom), float(lr), float(momentum), int(nesterov),
+                  int(first), int(inner_slot), _s(theta))
+
+    def unpack_adamw_fp4_rot(self, tree, bucket, slots, seed, theta, exp_avg, exp_avg_sq, scalars,
+                             inner_slot) -> None:
+        _lib.call("dl_unpack_adamw_fp4_rot", tree.handle, bucket, slots.data_ptr(), int(seed),
+                  theta.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars,
+                  int(inner_slot), _s(theta))
+
+    def decode_fp4_rot(self, tree, bucket, slots, seed, dst) -> None:
+        """dst (packed fp32) <- R⁻¹(deq(slots)) inside every chunk: the values the steps use."""
+        _lib.call("dl_decode_fp4_rot", tree.handle, bucket, slots.data_ptr(), int(seed),
+                  dst.data_ptr(), _s(dst))
+
     # top-k sparse wire codec (DL_TOPK_SLOT_BYTES(k) = 6k-byte slots, one per chunk; dl_topk.hip).
     # residual None: no error feedback
     def delta_topk(self, tree, bucket, inner_slot, theta, residual, k, slots) -> None:

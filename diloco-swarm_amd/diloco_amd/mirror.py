@@ -98,6 +98,10 @@ OUTER_WIRES = ("f32", "bf16", "int8", "fp4", "topk")
 # buffers and pipelining, and the residual arenas of error feedback.
 SLOT_WIRES = ("int8", "fp4", "topk")
 DEFAULT_TOPK = 64  # entries per chunk of the "topk" wire (DILOCO_OUTER_TOPK)
+# The fp4 wire's randomised Hadamard rotation (dl_fp4_rot.hip; DILOCO_OUTER_FP4_ROTATE, off if
+# unset): the seed of its signs (DILOCO_OUTER_FP4_SEED) must be the same on every rank -- a peer
+# that decodes with another seed reads noise.
+DEFAULT_FP4_SEED = 0x5EED
 # The DP exchange behind sync_gradients for the device outer model at N > 1:
 #   "sharded"     per bucket RCCL reduce_scatter -> Nesterov SGD on this rank's 1/n of θ and
 #                 the momentum -> RCCL all_gather of θ (20 + 20/n B/param of HBM)
@@ -694,7 +698,8 @@ class DeviceOuterMirror:
     def __init__(self, outer_model: torch.nn.Module, device: torch.device, kernels=None,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = False,
                  wire: str = "f32", exchange: str = "sharded", keep_params: bool = False,
-                 error_feedback: bool = False, topk: int = DEFAULT_TOPK):
+                 error_feedback: bool = False, topk: int = DEFAULT_TOPK, rotate: bool = False,
+                 rot_seed: int = DEFAULT_FP4_SEED):
         """keep_params: the outer model's Parameter objects stay the ones it has (their class
         switched to OuterParameter in place) -- for an outer model that got its device only
         at its first compute_pseudo_gradient, after get_optimizer took references to them.
@@ -712,6 +717,12 @@ class DeviceOuterMirror:
         # a residual) and the re-quantised average the owner's (dl_q8_reduce_ef; dl_fp4_reduce
         # with one); the arenas, of one shape for both wires, are made at the first exchange
         self.error_feedback = bool(error_feedback)
+        if rotate and wire != "fp4":
+            raise ValueError(f"rotate=True is the fp4 wire's Hadamard rotation; the wire is {wire!r}")
+        # fp4 wire: every encode, step and .grad read goes through the _rot kernels under this
+        # seed (the reduce is the plain one: the rotation is linear)
+        self.rotate = bool(rotate)
+        self.rot_seed = int(rot_seed) & 0xFFFFFFFF
         self.topk = int(topk)  # entries per chunk; the "topk" wire only
         if wire == "topk" and (self.topk % 8 or not _lib.TOPK_MIN_K <= self.topk <= _lib.TOPK_MAX_K):
             raise ValueError(f"topk {topk}: a multiple of 8 in [{_lib.TOPK_MIN_K}, "
@@ -1337,6 +1348,8 @@ class DeviceOuterMirror:
     def _slot_encode(self, b: int, slot: int, theta, residual, region) -> None:
         if self.wire == "topk":
             self.k.delta_topk(self.tree, b, slot, theta, residual, self.topk, region)
+        elif self.wire == "fp4" and self.rotate:
+            self.k.delta_fp4_rot(self.tree, b, slot, theta, residual, self.rot_seed, region)
         elif self.wire == "fp4":
             self.k.delta_fp4(self.tree, b, slot, theta, residual, region)
         elif residual is not None:
@@ -1455,7 +1468,9 @@ class DeviceOuterMirror:
         forms: every encode (either path) carries this rank's residual, the reduce its owner's;
         the slots, and so the optimizer passes and .grad, are used as without it.
         wire="fp4": the same walk with dl_delta_fp4, dl_fp4_reduce and dl_unpack_*_fp4 on
-        2176-B slots (_slot_encode, _slot_reduce); a residual handed in is error feedback."""
+        2176-B slots (_slot_encode, _slot_reduce); a residual handed in is error feedback. With
+        rotate the encoder, the steps and .grad's decode are the _rot kernels (dl_fp4_rot.hip);
+        the reduce, the slots and the residual arenas are the same."""
         if self._delta is not None:
             self._take_delta()
             self._relay_theta()
@@ -1516,6 +1531,10 @@ class DeviceOuterMirror:
         S, C = q["S"], S_CHUNK
         for b in range(self.tree.n_buckets):
             nch, m, base, _ = q["plan"][b]
+            if self.rotate:  # R⁻¹(deq(slot)) straight into .grad's arena, as the steps form it
+                self.k.decode_fp4_rot(self.tree, b, self._q8_region(q, b), self.rot_seed,
+                                      self.d_wire)
+                continue
             sl = q["slots"][base * S:(base + nch) * S].view(nch, S)
             if self.wire == "topk":
                 g = _decode_topk(sl, self.topk)
@@ -1547,6 +1566,11 @@ class DeviceOuterMirror:
                                        self.d_theta, mom, lr, momentum, nesterov, first,
                                        SLOT_INNER if write else -1)
                 continue
+            if self.rotate:
+                self.k.unpack_sgd_fp4_rot(self.tree, b, self._q8_region(q, b), self.rot_seed,
+                                          self.d_theta, mom, lr, momentum, nesterov, first,
+                                          SLOT_INNER if write else -1)
+                continue
             step = self.k.unpack_sgd_fp4 if self.wire == "fp4" else self.k.unpack_sgd_q8
             step(self.tree, b, self._q8_region(q, b), self.d_theta, mom, lr, momentum, nesterov,
                  first, SLOT_INNER if write else -1)
@@ -1568,6 +1592,11 @@ class DeviceOuterMirror:
                 self.k.unpack_adamw_topk(self.tree, b, self._q8_region(q, b), self.topk,
                                          self.d_theta, self.d_m1, self.d_m2, scalars,
                                          SLOT_INNER if write else -1)
+                continue
+            if self.rotate:
+                self.k.unpack_adamw_fp4_rot(self.tree, b, self._q8_region(q, b), self.rot_seed,
+                                            self.d_theta, self.d_m1, self.d_m2, scalars,
+                                            SLOT_INNER if write else -1)
                 continue
             step = self.k.unpack_adamw_fp4 if self.wire == "fp4" else self.k.unpack_adamw_q8
             step(self.tree, b, self._q8_region(q, b), self.d_theta, self.d_m1, self.d_m2, scalars,
@@ -1994,7 +2023,8 @@ class LazyHostOuterMirror:
     def __init__(self, outer_model: torch.nn.Module, device: torch.device, kernels=None,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = True,
                  wire: str = "f32", exchange: str = DEFAULT_EXCHANGE["host"],
-                 error_feedback: bool = False, topk: int = DEFAULT_TOPK):
+                 error_feedback: bool = False, topk: int = DEFAULT_TOPK, rotate: bool = False,
+                 rot_seed: int = DEFAULT_FP4_SEED):
         self.device = torch.device(device)
         params = module_params(outer_model)
         if not params:
@@ -2006,7 +2036,8 @@ class LazyHostOuterMirror:
                 torch.nn.Parameter(_DATA.__get__(p).to(self.device), p.requires_grad)
                 for p in params])
         self.dev = DeviceOuterMirror(twin, self.device, kernels, bucket_cap_elems, fused, wire,
-                                     exchange, error_feedback=error_feedback, topk=topk)
+                                     exchange, error_feedback=error_feedback, topk=topk,
+                                     rotate=rotate, rot_seed=rot_seed)
         self._twin = twin
         self.fused, self.wire, self.exchange = fused, wire, exchange
         from .utils import env_flag

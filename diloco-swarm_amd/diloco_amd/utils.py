@@ -81,7 +81,7 @@ import torch.nn as nn
 from torch.optim import SGD, AdamW, Optimizer
 
 from .kernels import default_kernels
-from .mirror import (DEFAULT_EXCHANGE, DEFAULT_TOPK, OUTER_EXCHANGES, OUTER_WIRES, SLOT_WIRES,
+from .mirror import (DEFAULT_EXCHANGE, DEFAULT_FP4_SEED, DEFAULT_TOPK, OUTER_EXCHANGES, OUTER_WIRES, SLOT_WIRES,
                      WRITE_BACKS, DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
 from .optim import InnerAdamW, OuterAdamW, OuterSGD
 from . import _lib
@@ -98,6 +98,7 @@ _EXCHANGE = "_diloco_exchange"
 _EXCHANGE_ASKED = "_diloco_exchange_asked"  # by argument or DILOCO_OUTER_EXCHANGE
 _Q8_EF = "_diloco_q8_ef"  # int8 wire with error feedback (DILOCO_OUTER_Q8_EF)
 _TOPK = "_diloco_topk"  # entries per chunk of the "topk" wire (DILOCO_OUTER_TOPK)
+_ROTATE = "_diloco_fp4_rotate"  # the fp4 wire's rotation seed when it is on, else None
 _ADAMW = "_diloco_adamw"  # an optim.OuterAdamW is attached
 OUTER_ADAMW = ("torch", "fused")
 INNER_ADAMW = ("torch", "fused")  # DILOCO_INNER_ADAMW: the inner optimizer's step
@@ -162,6 +163,8 @@ def outer_mirror(outer_model: nn.Module, device=None):
         ef = {"error_feedback": True} if getattr(outer_model, _Q8_EF, False) else {}
         if getattr(outer_model, _WIRE, "f32") == "topk":  # likewise named for its own wire only
             ef["topk"] = getattr(outer_model, _TOPK)
+        if getattr(outer_model, _ROTATE, None) is not None:  # likewise
+            ef.update(rotate=True, rot_seed=getattr(outer_model, _ROTATE))
         if getattr(outer_model, _PLACEMENT, "host") == "device":
             p = next(outer_model.parameters(), None)
             if p is None:
@@ -218,7 +221,7 @@ def _inner_device(inner_model: nn.Module) -> torch.device:
 def get_outer_model(inner_model: nn.Module, placement: str = None,
                     write_back: str = None, fused: bool = None, wire: str = None,
                     exchange: str = None, error_feedback: bool = None,
-                    topk: int = None) -> nn.Module:
+                    topk: int = None, rotate: bool = None) -> nn.Module:
     """Initializes the outer model from the inner model (src/utils.py:213-216).
 
     placement "host" (the reference's, default) or "device" (in HBM: on the inner model's GPU;
@@ -238,7 +241,13 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     every 4096-element chunk as exact fp32 values (dl_delta_topk, dl_topk_reduce,
     dl_unpack_sgd_topk / dl_unpack_adamw_topk); its error_feedback (None reads
     DILOCO_OUTER_TOPK_EF) is ON by default, for this wire only -- without it whatever was not
-    selected is lost -- and error_feedback=False is allowed."""
+    selected is lost -- and error_feedback=False is allowed. rotate (fp4 wire only; None reads
+    DILOCO_OUTER_FP4_ROTATE, default off): every 256-element block is multiplied by random signs
+    and Hadamard-transformed before the quantiser and transformed back after the decoder
+    (dl_delta_fp4_rot, dl_unpack_*_fp4_rot, dl_decode_fp4_rot for .grad), which makes the
+    wire's error independent of the data's distribution: smaller on heavy tails, larger where a
+    group already spans many binades. The signs come from DILOCO_OUTER_FP4_SEED (default
+    0x5EED), which MUST be the same on every rank. Error feedback composes as without it."""
     if placement is None:
         placement = os.environ.get("DILOCO_OUTER_PLACEMENT", "host")
     if placement not in PLACEMENTS:
@@ -260,6 +269,15 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     elif error_feedback and wire not in SLOT_WIRES:
         raise ValueError(f"error_feedback=True compensates the int8 / fp4 wire's quantiser; the "
                          f"wire is {wire!r}")
+    if rotate is None:  # consulted for its own wire only
+        rotate = wire == "fp4" and env_flag("DILOCO_OUTER_FP4_ROTATE", False)
+    elif rotate and wire != "fp4":
+        raise ValueError(f"rotate=True is the fp4 wire's Hadamard rotation; the wire is {wire!r}")
+    seed = None
+    if rotate:  # decimal or 0x..., a uint32
+        seed = int(os.environ.get("DILOCO_OUTER_FP4_SEED") or str(DEFAULT_FP4_SEED), 0)
+        if not 0 <= seed <= 0xFFFFFFFF:
+            raise ValueError(f"DILOCO_OUTER_FP4_SEED {seed}: a 32-bit unsigned integer")
     if wire == "topk":
         if topk is None:
             topk = int(os.environ.get("DILOCO_OUTER_TOPK") or DEFAULT_TOPK)
@@ -303,6 +321,7 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     object.__setattr__(outer_model, _WIRE, wire)
     object.__setattr__(outer_model, _Q8_EF, bool(error_feedback))
     object.__setattr__(outer_model, _TOPK, topk)
+    object.__setattr__(outer_model, _ROTATE, seed)
     object.__setattr__(outer_model, _EXCHANGE, exchange)
     object.__setattr__(outer_model, _EXCHANGE_ASKED, asked)
     if placement == "device" and has_params and not getattr(outer_model, _PENDING, False):

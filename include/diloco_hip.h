@@ -584,6 +584,59 @@ DL_API int dl_gather_fp4(dl_tree_t tree, int32_t bucket, int32_t src_slot,
 DL_API int dl_unpack_avg_fp4(dl_tree_t tree, int32_t bucket, const void* slots, int32_t dst_slot,
                              double* partials /* NULL: none */, dl_stream_t stream);
 
+/* ---- fp4 wire behind a randomised Hadamard rotation (not in the reference) -----------------
+ * One scale serves 32 elements, so one large element pushes the other 31 of its group onto the
+ * coarse end of the E2M1 grid. These entry points rotate every 256-element block of a chunk
+ * before the quantiser and back after the decoder, which spreads an outlier over its block. The
+ * slot format, the scale and nibble rules and dl_fp4_reduce are unchanged (R is linear: the sum
+ * of rotated slots is the rotated sum). Definition, for a uint32_t seed:
+ *   A chunk has DL_CHUNK_ELEMS positions i; positions at or past the chunk's length hold +0.
+ *   Block i >> 8, in-block index p = i & 255.
+ *   Sign of position i, all arithmetic mod 2^32:
+ *     h = (i + seed) * 0x9E3779B1; h ^= h >> 15; h *= 0x85EBCA77; h ^= h >> 13;
+ *     h *= 0xC2B2AE3D; h ^= h >> 16; sigma = h >> 31
+ *   R(x):   v[i] = sigma ? -x[i] : x[i]   (a sign-bit flip, exact); then for stages s = 0..7 in
+ *           that order, h = 1 << s, for every p with bit s clear: a = v[p], b = v[p + h];
+ *           v[p] = a + b; v[p + h] = a - b (one rounded fp32 operation each);
+ *           then y[i] = v[i] * 0.0625f (1/sqrt(256), exact).
+ *   R^-1(y): the same eight stages on y, then * 0.0625f, then the sign flips by sigma.
+ * R^-1(R(x)) equals x to rounding, not bit for bit, and nothing relies on it. There is no
+ * special case for non-finite values: a NaN or Inf anywhere in a block makes the block's 256
+ * rotated values non-finite, its eight groups get E = 255 and the block decodes to NaN; other
+ * blocks are untouched; a sum that overflows fp32 does the same by IEEE rules. The seed must be
+ * the same on every peer and for the encoder and the decoder of a slot.
+ * dl_delta_fp4_rot, per chunk c of the bucket and element k of the packed space:
+ *   x = outer[k] - inner[seg][j] (+ r[k]: two rounded operations, as dl_delta_fp4)
+ *   slot(c) <- enc(R(x)) over all DL_CHUNK_ELEMS rotated positions: a short chunk's last live
+ *   block has non-zero groups past the length, blocks wholly past it are zero bytes. Every byte
+ *   of every launched slot is written, and no byte of any other slot.
+ *   r[k] <- x - R^-1(deq(slot(c)))   (residual_packed not NULL; positions inside the chunk
+ *   only, in place, by the lane that read it: the residual stays in the original domain and its
+ *   padding is never written; what rounding puts on positions past the length is dropped, as
+ *   the decoder drops those positions)
+ * dl_unpack_sgd_fp4_rot / dl_unpack_adamw_fp4_rot: g = R^-1(deq(slot)) over whole blocks, then
+ * one element of dl_unpack_sgd / dl_unpack_adamw (divisor 1) and the inner write for positions
+ * inside the chunk only: bit-identical to decoding into an fp32 wire (dl_decode_fp4_rot) and
+ * running those kernels on it.
+ * dl_decode_fp4_rot: dst_packed[k] = R^-1(deq(slot(c)))[i] inside each chunk; the padding is
+ * not written.
+ * Results do not depend on the inner tensors' alignment, the grid or the bucket split. Pointer
+ * checks are the fp4 entry points'; any seed is valid. */
+DL_API int dl_delta_fp4_rot(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
+                            const float* outer_packed, float* residual_packed /* NULL: none */,
+                            uint32_t seed, void* slots, dl_stream_t stream);
+DL_API int dl_unpack_sgd_fp4_rot(dl_tree_t tree, int32_t bucket, const void* slots, uint32_t seed,
+                                 float* outer_packed, float* mom_packed, float lr, float momentum,
+                                 int32_t nesterov, int32_t first_step, int32_t inner_slot,
+                                 dl_stream_t stream);
+DL_API int dl_unpack_adamw_fp4_rot(dl_tree_t tree, int32_t bucket, const void* slots,
+                                   uint32_t seed, float* outer_packed, float* exp_avg_packed,
+                                   float* exp_avg_sq_packed, float decay, float w1, float beta2,
+                                   float w2, float neg_step_size, float bc2_sqrt, float eps,
+                                   int32_t inner_slot, dl_stream_t stream);
+DL_API int dl_decode_fp4_rot(dl_tree_t tree, int32_t bucket, const void* slots, uint32_t seed,
+                             float* dst_packed, dl_stream_t stream);
+
 /* ---- top-k sparse wire codec (not in the reference) ----------------------------------------
  * The pseudo-gradient exchange of the int8 / fp4 wires with a sparse slot: the k entries of
  * largest magnitude of each chunk, exact fp32 values, on the same slot plan, collectives and
