@@ -1194,73 +1194,114 @@ DL_API int dl_decode_fp4_rot(dl_tree_t t, int32_t b, const void* slots, uint32_t
   return e == hipSuccess ? DL_OK : hip_fail(e, "dl_decode_fp4_rot");
 }
 
-// The top-k wire (dl_topk.hip): the checks, launches and store policies of the fp4 calls, after
-// the check of k.
-DL_API int dl_delta_topk(dl_tree_t t, int32_t b, int32_t inner_slot, const float* outer,
-                         float* residual, int32_t k, void* slots, dl_stream_t s) {
+// The top-k wires (dl_topk.hip: exact values; dl_topk_fp4.hip: 4-bit values): the checks,
+// launches and store policies of the fp4 calls, after the check of k. One body per call for both
+// wires; `who` names the entry point in errors, `launch` is its wire's launcher.
+namespace {
+
+int delta_topk(const char* who, decltype(&dl::launch_delta_topk) launch, dl_tree_t t, int32_t b,
+               int32_t inner_slot, const float* outer, float* residual, int32_t k, void* slots,
+               dl_stream_t s) {
   dl::Launch L;
-  DL_TRY(check_topk_k(k, "dl_delta_topk"));
-  DL_TRY(make_launch(t, b, s, &L, "dl_delta_topk", kAutoDeltaQ8));
-  DL_TRY(check_slot(t, inner_slot, "dl_delta_topk"));
-  DL_TRY(check_packed(outer, "dl_delta_topk", "outer"));
-  if (residual) DL_TRY(check_packed(residual, "dl_delta_topk", "residual"));
-  DL_TRY(check_packed(slots, "dl_delta_topk", "slots"));
-  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_delta_topk"));
-  hipError_t e = dl::launch_delta_topk(L, inner_slot, outer, residual, k, static_cast<uint8_t*>(slots));
-  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_delta_topk")
-                         : hip_fail(e, "dl_delta_topk");
+  DL_TRY(check_topk_k(k, who));
+  DL_TRY(make_launch(t, b, s, &L, who, kAutoDeltaQ8));
+  DL_TRY(check_slot(t, inner_slot, who));
+  DL_TRY(check_packed(outer, who, "outer"));
+  if (residual) DL_TRY(check_packed(residual, who, "residual"));
+  DL_TRY(check_packed(slots, who, "slots"));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, who));
+  hipError_t e = launch(L, inner_slot, outer, residual, k, static_cast<uint8_t*>(slots));
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, who) : hip_fail(e, who);
 }
+
+int topk_reduce(const char* who, decltype(&dl::launch_topk_reduce) launch, const void* recv,
+                int32_t n, int32_t m, int32_t divisor, float* residual, int32_t k, void* out,
+                dl_stream_t s) {
+  DL_TRY(check_topk_k(k, who));
+  if (n < 1 || m < 0 || divisor < 1) return fail(DL_E_ARG, "%s: n %d m %d div %d", who, n, m, divisor);
+  DL_TRY(check_packed(recv, who, "recv"));
+  if (residual) DL_TRY(check_packed(residual, who, "residual"));
+  DL_TRY(check_packed(out, who, "out"));
+  if (recv == out && n != 1) return fail(DL_E_ARG, "%s: in place needs n_peers == 1", who);
+  hipError_t e = launch(static_cast<const uint8_t*>(recv), n, m, divisor, residual, k,
+                        static_cast<uint8_t*>(out), static_cast<hipStream_t>(s));
+  return e == hipSuccess ? DL_OK : hip_fail(e, who);
+}
+
+int unpack_sgd_topk(const char* who, decltype(&dl::launch_unpack_sgd_topk) launch, dl_tree_t t,
+                    int32_t b, const void* slots, int32_t k, float* outer, float* mom, float lr,
+                    float momentum, int32_t nesterov, int32_t first_step, int32_t inner_slot,
+                    dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_topk_k(k, who));
+  DL_TRY(make_launch(t, b, s, &L, who, kAutoNT));
+  DL_TRY(check_packed(slots, who, "slots"));
+  DL_TRY(check_packed(outer, who, "outer"));
+  dl::SgdArgs a;
+  DL_TRY(sgd_args(who, mom, lr, momentum, nesterov, first_step, &a));
+  DL_TRY(check_slot(t, inner_slot, who, true));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, who));
+  hipError_t e = launch(L, static_cast<const uint8_t*>(slots), k, outer, mom, a, inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, who) : hip_fail(e, who);
+}
+
+int unpack_adamw_topk(const char* who, decltype(&dl::launch_unpack_adamw_topk) launch, dl_tree_t t,
+                      int32_t b, const void* slots, int32_t k, float* outer, float* exp_avg,
+                      float* exp_avg_sq, dl::AdamArgs a, int32_t inner_slot, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_topk_k(k, who));
+  DL_TRY(make_launch(t, b, s, &L, who, kAutoNT));
+  DL_TRY(check_packed(slots, who, "slots"));
+  DL_TRY(check_packed(outer, who, "outer"));
+  DL_TRY(check_packed(exp_avg, who, "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, who, "exp_avg_sq"));
+  DL_TRY(check_slot(t, inner_slot, who, true));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, who));
+  hipError_t e = launch(L, static_cast<const uint8_t*>(slots), k, outer, exp_avg, exp_avg_sq, a,
+                        inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, who) : hip_fail(e, who);
+}
+
+}  // namespace
+
+#define DL_TOPK_ENTRY_POINTS(SFX)                                                                  \
+  DL_API int dl_delta_topk##SFX(dl_tree_t t, int32_t b, int32_t inner_slot, const float* outer,    \
+                                float* residual, int32_t k, void* slots, dl_stream_t s) {          \
+    return delta_topk("dl_delta_topk" #SFX, dl::launch_delta_topk##SFX, t, b, inner_slot, outer,   \
+                      residual, k, slots, s);                                                      \
+  }                                                                                                \
+  DL_API int dl_unpack_sgd_topk##SFX(dl_tree_t t, int32_t b, const void* slots, int32_t k,         \
+                                     float* outer, float* mom, float lr, float momentum,           \
+                                     int32_t nesterov, int32_t first_step, int32_t inner_slot,     \
+                                     dl_stream_t s) {                                              \
+    return unpack_sgd_topk("dl_unpack_sgd_topk" #SFX, dl::launch_unpack_sgd_topk##SFX, t, b,       \
+                           slots, k, outer, mom, lr, momentum, nesterov, first_step, inner_slot,   \
+                           s);                                                                     \
+  }                                                                                                \
+  DL_API int dl_unpack_adamw_topk##SFX(dl_tree_t t, int32_t b, const void* slots, int32_t k,       \
+                                       float* outer, float* exp_avg, float* exp_avg_sq,            \
+                                       float decay, float w1, float beta2, float w2,               \
+                                       float neg_step_size, float bc2_sqrt, float eps,             \
+                                       int32_t inner_slot, dl_stream_t s) {                        \
+    return unpack_adamw_topk("dl_unpack_adamw_topk" #SFX, dl::launch_unpack_adamw_topk##SFX, t, b, \
+                             slots, k, outer, exp_avg, exp_avg_sq,                                 \
+                             dl::AdamArgs{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps},     \
+                             inner_slot, s);                                                       \
+  }
+DL_TOPK_ENTRY_POINTS()
+DL_TOPK_ENTRY_POINTS(_fp4)
+#undef DL_TOPK_ENTRY_POINTS
 
 DL_API int dl_topk_reduce(const void* recv, int32_t n, int32_t m, int32_t divisor, float* residual,
                           int32_t k, void* out, dl_stream_t s) {
-  DL_TRY(check_topk_k(k, "dl_topk_reduce"));
-  if (n < 1 || m < 0 || divisor < 1)
-    return fail(DL_E_ARG, "dl_topk_reduce: n %d m %d div %d", n, m, divisor);
-  DL_TRY(check_packed(recv, "dl_topk_reduce", "recv"));
-  if (residual) DL_TRY(check_packed(residual, "dl_topk_reduce", "residual"));
-  DL_TRY(check_packed(out, "dl_topk_reduce", "out"));
-  if (recv == out && n != 1) return fail(DL_E_ARG, "dl_topk_reduce: in place needs n_peers == 1");
-  hipError_t e = dl::launch_topk_reduce(static_cast<const uint8_t*>(recv), n, m, divisor, residual,
-                                        k, static_cast<uint8_t*>(out), static_cast<hipStream_t>(s));
-  return e == hipSuccess ? DL_OK : hip_fail(e, "dl_topk_reduce");
+  return topk_reduce("dl_topk_reduce", dl::launch_topk_reduce, recv, n, m, divisor, residual, k,
+                     out, s);
 }
 
-DL_API int dl_unpack_sgd_topk(dl_tree_t t, int32_t b, const void* slots, int32_t k, float* outer,
-                              float* mom, float lr, float momentum, int32_t nesterov,
-                              int32_t first_step, int32_t inner_slot, dl_stream_t s) {
-  dl::Launch L;
-  DL_TRY(check_topk_k(k, "dl_unpack_sgd_topk"));
-  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_sgd_topk", kAutoNT));
-  DL_TRY(check_packed(slots, "dl_unpack_sgd_topk", "slots"));
-  DL_TRY(check_packed(outer, "dl_unpack_sgd_topk", "outer"));
-  dl::SgdArgs a;
-  DL_TRY(sgd_args("dl_unpack_sgd_topk", mom, lr, momentum, nesterov, first_step, &a));
-  DL_TRY(check_slot(t, inner_slot, "dl_unpack_sgd_topk", true));
-  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_sgd_topk"));
-  hipError_t e = dl::launch_unpack_sgd_topk(L, static_cast<const uint8_t*>(slots), k, outer, mom, a,
-                                            inner_slot);
-  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_sgd_topk")
-                         : hip_fail(e, "dl_unpack_sgd_topk");
-}
-
-DL_API int dl_unpack_adamw_topk(dl_tree_t t, int32_t b, const void* slots, int32_t k, float* outer,
-                                float* exp_avg, float* exp_avg_sq, float decay, float w1,
-                                float beta2, float w2, float neg_step_size, float bc2_sqrt,
-                                float eps, int32_t inner_slot, dl_stream_t s) {
-  dl::Launch L;
-  DL_TRY(check_topk_k(k, "dl_unpack_adamw_topk"));
-  DL_TRY(make_launch(t, b, s, &L, "dl_unpack_adamw_topk", kAutoNT));
-  DL_TRY(check_packed(slots, "dl_unpack_adamw_topk", "slots"));
-  DL_TRY(check_packed(outer, "dl_unpack_adamw_topk", "outer"));
-  DL_TRY(check_packed(exp_avg, "dl_unpack_adamw_topk", "exp_avg"));
-  DL_TRY(check_packed(exp_avg_sq, "dl_unpack_adamw_topk", "exp_avg_sq"));
-  DL_TRY(check_slot(t, inner_slot, "dl_unpack_adamw_topk", true));
-  dl::AdamArgs a{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps};
-  DL_TRY(slot_begin(t, inner_slot, L.stream, "dl_unpack_adamw_topk"));
-  hipError_t e = dl::launch_unpack_adamw_topk(L, static_cast<const uint8_t*>(slots), k, outer,
-                                              exp_avg, exp_avg_sq, a, inner_slot);
-  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, "dl_unpack_adamw_topk")
-                         : hip_fail(e, "dl_unpack_adamw_topk");
+DL_API int dl_topk_fp4_reduce(const void* recv, int32_t n, int32_t m, int32_t divisor,
+                              float* residual, int32_t k, void* out, dl_stream_t s) {
+  return topk_reduce("dl_topk_fp4_reduce", dl::launch_topk_fp4_reduce, recv, n, m, divisor,
+                     residual, k, out, s);
 }
 
 DL_API int dl_gather(dl_tree_t t, int32_t b, int32_t src_slot, void* packed, int32_t dtype,

@@ -145,6 +145,15 @@ hipError_t launch_unpack_sgd_topk(const Launch& L, const uint8_t* slots, int k, 
                                   float* mom, SgdArgs a, int inner_slot);
 hipError_t launch_unpack_adamw_topk(const Launch& L, const uint8_t* slots, int k, float* outer,
                                     float* m1, float* m2, AdamArgs a, int inner_slot);
+// the top-k wire with 4-bit values (dl_topk_fp4.hip): the same calls on (16 + 2k)-byte slots
+hipError_t launch_delta_topk_fp4(const Launch& L, int inner_slot, const float* outer, float* resid,
+                                 int k, uint8_t* slots);
+hipError_t launch_topk_fp4_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,
+                                  float* resid, int32_t k, uint8_t* out, hipStream_t s);
+hipError_t launch_unpack_sgd_topk_fp4(const Launch& L, const uint8_t* slots, int k, float* outer,
+                                      float* mom, SgdArgs a, int inner_slot);
+hipError_t launch_unpack_adamw_topk_fp4(const Launch& L, const uint8_t* slots, int k, float* outer,
+                                        float* m1, float* m2, AdamArgs a, int inner_slot);
 // the gradient side of the fp4 exchange (dl_fp4_grad.hip): launch_gather_q8 /
 // launch_unpack_avg_q8 on the fp4 slots
 hipError_t launch_gather_fp4(const Launch& L, int src_slot, float* resid, uint8_t* slots);

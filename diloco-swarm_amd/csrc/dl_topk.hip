@@ -101,107 +101,6 @@ struct DeltaTopk {
   }
 };
 
-// a4 + a5 from the averaged top-k slots under either rule (SgdRule<MODE>, AdamRule of
-// dl_outer_step.h: the arithmetic of dl_unpack_sgd / dl_unpack_adamw). The slot's entries are
-// loaded (one per lane, non-temporal) ahead of the loads of θ and the state, scattered into the
-// zeroed dense chunk in LDS, and every lane takes its rows of the gradient from it; the rule
-// runs on every element inside the chunk (a zero gradient still decays momentum) and the stores
-// leave one stream at a time: θ, the state, inner.
-template <class Rule>
-struct UnpackTopk {
-  static constexpr int K = Rule::kStates;
-  const uint8_t* slots;
-  int c0;
-  float* outer;
-  Rule rule;
-  int inner_slot;
-  int k;
-
-  template <int J>
-  __device__ __forceinline__ void step(float g, float4 (&m)[K][kUnroll], int u, float4& t) const {
-    float e[K];
-#pragma unroll
-    for (int s = 0; s < K; ++s) e[s] = Rule::kLoadState ? comp<J>(m[s][u]) : 0.f;
-    rule.apply(g, e, comp<J>(t));
-#pragma unroll
-    for (int s = 0; s < K; ++s) comp<J>(m[s][u]) = e[s];
-  }
-
-  template <bool NTL, int NTS>
-  __device__ __forceinline__ void run(const Chunk& ck, int c, void* const* caddr, int nchunk, int tid) const {
-    __shared__ float4 dense4[DL_CHUNK_ELEMS / 4];
-    float* dense = reinterpret_cast<float*>(dense4);
-    float* in = inner_slot >= 0 ? slot_ptr<float>(caddr, nchunk, inner_slot, c) : nullptr;
-    const uint8_t* slot = slots + size_t(c - c0) * DL_TOPK_SLOT_BYTES(k);
-    float* th = outer + ck.poff;
-    float* sp[K];
-#pragma unroll
-    for (int s = 0; s < K; ++s) sp[s] = rule.state(s) + ck.poff;
-    auto one = [&](int i, float g) {
-      float t1 = th[i];
-      float e[K];
-#pragma unroll
-      for (int s = 0; s < K; ++s) e[s] = Rule::kLoadState ? sp[s][i] : 0.f;
-      rule.apply(g, e, t1);
-      th[i] = t1;
-      if (Rule::kStoreState) {
-#pragma unroll
-        for (int s = 0; s < K; ++s) sp[s][i] = e[s];
-      }
-      if (in) in[i] = t1;
-    };
-    TopkEntry en = {0.f, 0u};
-    if (tid < k) en = topk_entry(slot, k, tid);
-    const bool rows = in == nullptr || aligned16(in);
-    const int nv = ck.len >> 2;
-    float4 t[kUnroll], m[K][kUnroll], g[kUnroll];
-    if (rows) {
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int v = u * kThreads + tid;
-        if (v < nv) {
-          t[u] = ldf4<NTL>(th, v);
-          if (Rule::kLoadState) {
-#pragma unroll
-            for (int s = 0; s < K; ++s) m[s][u] = ldf4<NTL>(sp[s], v);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) dense4[u * kThreads + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
-    if (tid < k) dense[en.idx] = en.val;
-    __syncthreads();
-    if (rows) {
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) g[u] = dense4[u * kThreads + tid];
-      const int i = (nv << 2) + tid;  // the < 4 elements past the last float4, one per lane
-      const float gt = i < ck.len ? dense[i] : 0.f;
-      __syncthreads();  // the dense chunk is reused by the workgroup's next chunk
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        if (u * kThreads + tid < nv) {
-          step<0>(g[u].x, m, u, t[u]);
-          step<1>(g[u].y, m, u, t[u]);
-          step<2>(g[u].z, m, u, t[u]);
-          step<3>(g[u].w, m, u, t[u]);
-        }
-      }
-      store_rows<NTS>(th, t, nv, tid);
-      if (Rule::kStoreState) {
-#pragma unroll
-        for (int s = 0; s < K; ++s) store_rows<NTS>(sp[s], m[s], nv, tid);
-      }
-      if (in) store_rows<NTS>(in, t, nv, tid);
-      if (i < ck.len) one(i, gt);
-    } else {
-      for (int i = tid; i < ck.len; i += kThreads) one(i, dense[i]);
-      __syncthreads();
-    }
-  }
-};
-
 // Σ over n peers' copies of m slots (recv laid out [peer][slot]) -> averaged slots, selected
 // again; one workgroup per slot. The accumulator is the dense chunk in LDS: per peer, in rank
 // order, lane e adds entry e at its index (one rounded add per entry; an all-zero slot has k
@@ -261,13 +160,13 @@ hipError_t launch_delta_topk(const Launch& L, int inner_slot, const float* outer
 hipError_t launch_unpack_sgd_topk(const Launch& L, const uint8_t* slots, int k, float* outer,
                                   float* mom, SgdArgs a, int inner_slot) {
   return with_sgd_rule(mom, a, [&](auto rule) {
-    return run(L, UnpackTopk<decltype(rule)>{slots, L.c0, outer, rule, inner_slot, k});
+    return run(L, UnpackTopk<decltype(rule), TopkF32>{slots, L.c0, outer, rule, inner_slot, k});
   });
 }
 
 hipError_t launch_unpack_adamw_topk(const Launch& L, const uint8_t* slots, int k, float* outer,
                                     float* m1, float* m2, AdamArgs a, int inner_slot) {
-  return run(L, UnpackTopk<AdamRule>{slots, L.c0, outer, AdamRule{m1, m2, a}, inner_slot, k});
+  return run(L, UnpackTopk<AdamRule, TopkF32>{slots, L.c0, outer, AdamRule{m1, m2, a}, inner_slot, k});
 }
 
 hipError_t launch_topk_reduce(const uint8_t* recv, int32_t n, int32_t m, int32_t divisor,

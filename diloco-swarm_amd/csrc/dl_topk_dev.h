@@ -1,6 +1,7 @@
 // Device-side pieces of the top-k sparse wire codec of dl_topk.hip: the selection of the k
 // largest keys of a chunk inside the workgroup that holds it in registers, the staged slot's
-// 16-B stores, and the decode of a slot into a dense chunk in LDS. Slot layout and rules are
+// 16-B stores, the decode of a slot into a dense chunk in LDS, and the fused optimizer pass over
+// it (UnpackTopk, shared with the 4-bit-value slot of dl_topk_fp4.hip). Slot layout and rules are
 // stated in include/diloco_hip.h. Nothing here rounds: keys are integer views of the values, the
 // slot carries the values' own bits.
 //
@@ -63,11 +64,63 @@ __device__ __forceinline__ void set_elem(float4& v, int j, float a) {
   else v.w = a;
 }
 
+// What a selection leaves in a lane's registers for another walk over its 16 components: the
+// threshold (prefix under mask, `need` ties taken) and the counts in index order ahead of the
+// lane, per (group, wave) in lane g·kWaves + w of `ex`, inside the wave in below[g].
+template <bool ROWS>
+struct TopkRanks {
+  static constexpr int kGroups = ROWS ? kUnroll : 4 * kUnroll;
+  uint32_t prefix, mask, need, ex;
+  uint32_t below[kGroups];
+};
+
+// group g (a row u, or an element row 4u + j) of the lane's components against the threshold:
+// R.below[g] <- the lanes below in the wave, the wave's total returned; ties in the low half,
+// keys above the threshold in the high half.
+template <bool ROWS>
+__device__ __forceinline__ uint32_t topk_group_counts(const float4 (&x)[kUnroll], TopkRanks<ROWS>& R, int g) {
+  uint32_t b = 0u, tot = 0u;
+#pragma unroll
+  for (int j = 0; j < (ROWS ? 4 : 1); ++j) {
+    const uint32_t m = topk_key(ROWS ? elem(x[g], j) : elem(x[g >> 2], g & 3)) & R.mask;
+    const uint64_t bg = __ballot(m > R.prefix), be = __ballot(m == R.prefix);
+    b += (lanes_below(bg) << 16) | lanes_below(be);
+    tot += (uint32_t(__builtin_popcountll(bg)) << 16) | uint32_t(__builtin_popcountll(be));
+  }
+  R.below[g] = b;
+  return tot;
+}
+
+// the lane's components in index order: f(u, j, value, position, rank) for every selected one
+// (f may rewrite x[u] component j)
+template <bool ROWS, class Fn>
+__device__ __forceinline__ void topk_walk(float4 (&x)[kUnroll], const TopkRanks<ROWS>& R, int tid, Fn&& f) {
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll
+  for (int g = 0; g < TopkRanks<ROWS>::kGroups; ++g) {
+    uint32_t run = lane_get(R.ex, g * kWaves + w) + R.below[g];
+#pragma unroll
+    for (int j = 0; j < (ROWS ? 4 : 1); ++j) {
+      const int u = ROWS ? g : g >> 2, jj = ROWS ? j : g & 3;
+      const float val = elem(x[u], jj);
+      const uint32_t m = topk_key(val) & R.mask;
+      const uint32_t ties = run & 0xffffu;
+      if (m > R.prefix || (m == R.prefix && ties < R.need)) {
+        const uint32_t rank = (run >> 16) + (ties < R.need ? ties : R.need);
+        f(u, jj, val, uint32_t(ROWS ? 4 * (g * kThreads + tid) + j : g * kThreads + tid), rank);
+      }
+      run += m > R.prefix ? 0x10000u : m == R.prefix ? 1u : 0u;
+    }
+  }
+}
+
 // x[u] component j is position 4(u·kThreads + tid) + j (ROWS) or (4u + j)·kThreads + tid of the
 // chunk. Stages the slot of the k first-ranked positions in L.stage; CLEAR: the selected
-// components of x become +0 (the residual). No barrier at the end: topk_store_slot has it.
+// components of x become +0 (the residual). No barrier at the end: topk_store_slot has it. R keeps
+// the ranks for a caller that walks the components again (dl_topk_fp4_dev.h).
 template <bool ROWS, bool CLEAR>
-__device__ __forceinline__ void topk_select(float4 (&x)[kUnroll], int k, TopkLds& L, int tid) {
+__device__ __forceinline__ void topk_select(float4 (&x)[kUnroll], int k, TopkLds& L, int tid,
+                                            TopkRanks<ROWS>& R) {
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
@@ -129,23 +182,11 @@ __device__ __forceinline__ void topk_select(float4 (&x)[kUnroll], int k, TopkLds
 
   // counts in index order: per group (a row u, or an element row 4u + j) the lanes below and the
   // wave's total, ties in the low half, keys above the threshold in the high half
-  constexpr int kGroups = ROWS ? kUnroll : 4 * kUnroll;
-  auto at = [&](int g, int j) -> float {
-    if constexpr (ROWS) return elem(x[g], j);
-    else return elem(x[g >> 2], g & 3);
-  };
-  uint32_t below[kGroups];
+  constexpr int kGroups = TopkRanks<ROWS>::kGroups;
+  R.prefix = prefix, R.mask = mask, R.need = need;
 #pragma unroll
   for (int g = 0; g < kGroups; ++g) {
-    uint32_t b = 0u, tot = 0u;
-#pragma unroll
-    for (int j = 0; j < (ROWS ? 4 : 1); ++j) {
-      const uint32_t m = topk_key(at(g, j)) & mask;
-      const uint64_t bg = __ballot(m > prefix), be = __ballot(m == prefix);
-      b += (lanes_below(bg) << 16) | lanes_below(be);
-      tot += (uint32_t(__builtin_popcountll(bg)) << 16) | uint32_t(__builtin_popcountll(be));
-    }
-    below[g] = b;
+    const uint32_t tot = topk_group_counts<ROWS>(x, R, g);
     if (lane == 0) L.wtab[g * kWaves + w] = tot;
   }
   __syncthreads();
@@ -156,27 +197,19 @@ __device__ __forceinline__ void topk_select(float4 (&x)[kUnroll], int k, TopkLds
     const uint32_t v = uint32_t(__shfl_up(int(ex), o, 64));
     if (lane >= o) ex += v;
   }
-  ex -= tv;
+  R.ex = ex - tv;
   uint32_t* sv = reinterpret_cast<uint32_t*>(L.stage);
   uint16_t* si = reinterpret_cast<uint16_t*>(sv + k);
-#pragma unroll
-  for (int g = 0; g < kGroups; ++g) {
-    uint32_t run = lane_get(ex, g * kWaves + w) + below[g];
-#pragma unroll
-    for (int j = 0; j < (ROWS ? 4 : 1); ++j) {
-      const int u = ROWS ? g : g >> 2, jj = ROWS ? j : g & 3;
-      const float val = at(g, j);
-      const uint32_t m = topk_key(val) & mask;
-      const uint32_t ties = run & 0xffffu;
-      if (m > prefix || (m == prefix && ties < need)) {
-        const uint32_t rank = (run >> 16) + (ties < need ? ties : need);
-        sv[rank] = __float_as_uint(val);
-        si[rank] = uint16_t(ROWS ? 4 * (g * kThreads + tid) + j : g * kThreads + tid);
-        if constexpr (CLEAR) set_elem(x[u], jj, 0.f);
-      }
-      run += m > prefix ? 0x10000u : m == prefix ? 1u : 0u;
-    }
-  }
+  topk_walk<ROWS>(x, R, tid, [&](int u, int j, float val, uint32_t pos, uint32_t rank) {
+    sv[rank] = __float_as_uint(val);
+    si[rank] = uint16_t(pos);
+    if constexpr (CLEAR) set_elem(x[u], j, 0.f);
+  });
+}
+template <bool ROWS, bool CLEAR>
+__device__ __forceinline__ void topk_select(float4 (&x)[kUnroll], int k, TopkLds& L, int tid) {
+  TopkRanks<ROWS> R;
+  topk_select<ROWS, CLEAR>(x, k, L, tid, R);
 }
 
 // the staged slot leaves as 6k/16 gap-free 16-B stores; the barriers order the staging before
@@ -206,6 +239,117 @@ __device__ __forceinline__ TopkEntry topk_entry(const uint8_t* slot, int k, int 
   const DL_GLOBAL uint16_t* i = (const DL_GLOBAL uint16_t*)(slot + 4 * k);
   return {__builtin_nontemporal_load(v + e), uint32_t(__builtin_nontemporal_load(i + e)) & (DL_CHUNK_ELEMS - 1)};
 }
+
+// the exact-value top-k slot as UnpackTopk's codec
+struct TopkF32 {
+  static __device__ __forceinline__ size_t slot_bytes(int k) { return size_t(DL_TOPK_SLOT_BYTES(k)); }
+  static __device__ __forceinline__ TopkEntry entry(const uint8_t* slot, int k, int e) {
+    return topk_entry(slot, k, e);
+  }
+};
+
+// a4 + a5 from the averaged top-k slots under either rule (SgdRule<MODE>, AdamRule of
+// dl_outer_step.h: the arithmetic of dl_unpack_sgd / dl_unpack_adamw). The slot's entries are
+// loaded (one per lane, non-temporal) ahead of the loads of θ and the state, scattered into the
+// zeroed dense chunk in LDS, and every lane takes its rows of the gradient from it; the rule
+// runs on every element inside the chunk (a zero gradient still decays momentum) and the stores
+// leave one stream at a time: θ, the state, inner. Codec (TopkF32; TopkFp4 of
+// dl_topk_fp4_dev.h) is the slot's size and the decode of one entry: the only place the two
+// top-k wires differ here.
+template <class Rule, class Codec>
+struct UnpackTopk {
+  static constexpr int K = Rule::kStates;
+  const uint8_t* slots;
+  int c0;
+  float* outer;
+  Rule rule;
+  int inner_slot;
+  int k;
+
+  template <int J>
+  __device__ __forceinline__ void step(float g, float4 (&m)[K][kUnroll], int u, float4& t) const {
+    float e[K];
+#pragma unroll
+    for (int s = 0; s < K; ++s) e[s] = Rule::kLoadState ? comp<J>(m[s][u]) : 0.f;
+    rule.apply(g, e, comp<J>(t));
+#pragma unroll
+    for (int s = 0; s < K; ++s) comp<J>(m[s][u]) = e[s];
+  }
+
+  template <bool NTL, int NTS>
+  __device__ __forceinline__ void run(const Chunk& ck, int c, void* const* caddr, int nchunk, int tid) const {
+    __shared__ float4 dense4[DL_CHUNK_ELEMS / 4];
+    float* dense = reinterpret_cast<float*>(dense4);
+    float* in = inner_slot >= 0 ? slot_ptr<float>(caddr, nchunk, inner_slot, c) : nullptr;
+    const uint8_t* slot = slots + size_t(c - c0) * Codec::slot_bytes(k);
+    float* th = outer + ck.poff;
+    float* sp[K];
+#pragma unroll
+    for (int s = 0; s < K; ++s) sp[s] = rule.state(s) + ck.poff;
+    auto one = [&](int i, float g) {
+      float t1 = th[i];
+      float e[K];
+#pragma unroll
+      for (int s = 0; s < K; ++s) e[s] = Rule::kLoadState ? sp[s][i] : 0.f;
+      rule.apply(g, e, t1);
+      th[i] = t1;
+      if (Rule::kStoreState) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) sp[s][i] = e[s];
+      }
+      if (in) in[i] = t1;
+    };
+    TopkEntry en = {0.f, 0u};
+    if (tid < k) en = Codec::entry(slot, k, tid);
+    const bool rows = in == nullptr || aligned16(in);
+    const int nv = ck.len >> 2;
+    float4 t[kUnroll], m[K][kUnroll], g[kUnroll];
+    if (rows) {
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const int v = u * kThreads + tid;
+        if (v < nv) {
+          t[u] = ldf4<NTL>(th, v);
+          if (Rule::kLoadState) {
+#pragma unroll
+            for (int s = 0; s < K; ++s) m[s][u] = ldf4<NTL>(sp[s], v);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) dense4[u * kThreads + tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    if (tid < k) dense[en.idx] = en.val;
+    __syncthreads();
+    if (rows) {
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) g[u] = dense4[u * kThreads + tid];
+      const int i = (nv << 2) + tid;  // the < 4 elements past the last float4, one per lane
+      const float gt = i < ck.len ? dense[i] : 0.f;
+      __syncthreads();  // the dense chunk is reused by the workgroup's next chunk
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        if (u * kThreads + tid < nv) {
+          step<0>(g[u].x, m, u, t[u]);
+          step<1>(g[u].y, m, u, t[u]);
+          step<2>(g[u].z, m, u, t[u]);
+          step<3>(g[u].w, m, u, t[u]);
+        }
+      }
+      store_rows<NTS>(th, t, nv, tid);
+      if (Rule::kStoreState) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) store_rows<NTS>(sp[s], m[s], nv, tid);
+      }
+      if (in) store_rows<NTS>(in, t, nv, tid);
+      if (i < ck.len) one(i, gt);
+    } else {
+      for (int i = tid; i < ck.len; i += kThreads) one(i, dense[i]);
+      __syncthreads();
+    }
+  }
+};
 
 }  // namespace
 }  // namespace dl

@@ -35,6 +35,11 @@ def TOPK_SLOT_BYTES(k: int) -> int:
     return 6 * k
 
 
+def TOPK_FP4_SLOT_BYTES(k: int) -> int:
+    """DL_TOPK_FP4_SLOT_BYTES(k): 8 scale bytes, 8 zero bytes, k u16 entries."""
+    return 16 + 2 * k
+
+
 def COPY_STREAMS(s: int) -> int:
     """DL_COPY_STREAMS(s): the read / write probe over s equal streams (1..4)."""
     return ((s - 1) & 3) << 8
@@ -161,6 +166,16 @@ SIGNATURES = {
         ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
     ),
     "dl_unpack_adamw_topk": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32,
+         _vp],
+    ),
+    "dl_delta_topk_fp4": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "dl_topk_fp4_reduce": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "dl_unpack_sgd_topk_fp4": (
+        ctypes.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
+    ),
+    "dl_unpack_adamw_topk_fp4": (
         ctypes.c_int,
         [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32,
          _vp],

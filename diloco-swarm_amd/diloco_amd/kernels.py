@@ -333,6 +333,30 @@ class HipKernels:
                   theta.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars,
                   int(inner_slot), _s(theta))
 
+    # top-k wire with 4-bit values (DL_TOPK_FP4_SLOT_BYTES(k) = 16 + 2k-byte slots;
+    # dl_topk_fp4.hip): the four calls above with each entry as index | E2M1 nibble << 12
+    def delta_topk_fp4(self, tree, bucket, inner_slot, theta, residual, k, slots) -> None:
+        """slots <- the k largest-magnitude entries of x per chunk, quantised per group of 32
+        entries; residual <- x - deq at the selected positions, x elsewhere, in place."""
+        _lib.call("dl_delta_topk_fp4", tree.handle, bucket, inner_slot, theta.data_ptr(),
+                  _ptr(residual), int(k), slots.data_ptr(), _s(theta))
+
+    def topk_fp4_reduce(self, recv, n_peers, n_slots, divisor, residual, k, out) -> None:
+        _lib.call("dl_topk_fp4_reduce", recv.data_ptr(), int(n_peers), int(n_slots), int(divisor),
+                  _ptr(residual), int(k), out.data_ptr(), _s(out))
+
+    def unpack_sgd_topk_fp4(self, tree, bucket, slots, k, theta, mom, lr, momentum, nesterov,
+                            first, inner_slot) -> None:
+        _lib.call("dl_unpack_sgd_topk_fp4", tree.handle, bucket, slots.data_ptr(), int(k),
+                  theta.data_ptr(), _ptr(mom), float(lr), float(momentum), int(nesterov),
+                  int(first), int(inner_slot), _s(theta))
+
+    def unpack_adamw_topk_fp4(self, tree, bucket, slots, k, theta, exp_avg, exp_avg_sq, scalars,
+                              inner_slot) -> None:
+        _lib.call("dl_unpack_adamw_topk_fp4", tree.handle, bucket, slots.data_ptr(), int(k),
+                  theta.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars,
+                  int(inner_slot), _s(theta))
+
     # the gradient side of the int8 exchange (dl_q8_grad.hip)
     def gather_q8(self, tree, bucket, src_slot, slots) -> None:
         """slots <- quantise(the gradients bound to src_slot), one slot per chunk."""

@@ -47,16 +47,10 @@ ALL = _lib.ALL_BUCKETS
 S_CHUNK = _lib.CHUNK_ELEMS  # elements per tree chunk (one int8 slot each)
 
 
-def _decode_fp4(sl: torch.Tensor) -> torch.Tensor:
-    """[nch, DL_FP4_SLOT_BYTES] slots -> [nch, 4096] fp32, the values dl_unpack_*_fp4 form in
-    registers: ±grid[code]·2^(E-127), NaN for a group with E = 255. The bits are put together
-    with integer ops (code = 2·ee + mm is E2M1: exponent field ee, mantissa bit mm), so no
-    denormal passes through floating-point arithmetic."""
-    nch = sl.shape[0]
-    G = S_CHUNK // 32
-    e = sl[:, :G].to(torch.int32).repeat_interleave(32, dim=1)
-    pay = sl[:, G:].to(torch.int32)
-    nib = torch.stack((pay & 15, pay >> 4), dim=-1).reshape(nch, S_CHUNK)
+def _fp4_bits(nib: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """int32 nibbles and their scale bytes -> the fp32 bits of ±grid[code]·2^(E-127), NaN for
+    E = 255. The bits are put together with integer ops (code = 2·ee + mm is E2M1: exponent field
+    ee, mantissa bit mm), so no denormal passes through floating-point arithmetic."""
     code = nib & 7
     # 2·grid[code] = (1 + half/2)·2^p with p = code >> 1 (code 1, the E2M1 subnormal, is 1·2^0)
     half = (code & 1) * (code > 1)
@@ -65,8 +59,18 @@ def _decode_fp4(sl: torch.Tensor) -> torch.Tensor:
     denormal = (2 + half) << (21 + be).clamp(min=0, max=21)  # be = 0 or -1 (E <= 1)
     bits = torch.where(be >= 1, normal, denormal)
     bits = torch.where(code == 0, torch.zeros_like(bits), bits | ((nib & 8) << 28))
-    bits = torch.where(e == 255, torch.full_like(bits, 0x7FC00000), bits)
-    return bits.view(torch.float32)
+    return torch.where(e == 255, torch.full_like(bits, 0x7FC00000), bits)
+
+
+def _decode_fp4(sl: torch.Tensor) -> torch.Tensor:
+    """[nch, DL_FP4_SLOT_BYTES] slots -> [nch, 4096] fp32, the values dl_unpack_*_fp4 form in
+    registers: ±grid[code]·2^(E-127), NaN for a group with E = 255."""
+    nch = sl.shape[0]
+    G = S_CHUNK // 32
+    e = sl[:, :G].to(torch.int32).repeat_interleave(32, dim=1)
+    pay = sl[:, G:].to(torch.int32)
+    nib = torch.stack((pay & 15, pay >> 4), dim=-1).reshape(nch, S_CHUNK)
+    return _fp4_bits(nib, e).view(torch.float32)
 
 
 def _decode_topk(sl: torch.Tensor, k: int) -> torch.Tensor:
@@ -78,6 +82,17 @@ def _decode_topk(sl: torch.Tensor, k: int) -> torch.Tensor:
     out = torch.zeros(nch, S_CHUNK, dtype=torch.int32, device=sl.device)
     # entries in order, so an all-zero slot (k entries at index 0, all +0) decodes to zeros
     out.scatter_(1, idx, val)
+    return out.view(torch.float32)
+
+
+def _decode_topk_fp4(sl: torch.Tensor, k: int) -> torch.Tensor:
+    """[nch, 16 + 2k] top-k slots with 4-bit values -> [nch, 4096] fp32: +0 with the decoded
+    entry e (index | nibble << 12, under the scale byte of entry group e // 32) at its index."""
+    nch = sl.shape[0]
+    ent = sl[:, 16:16 + 2 * k].contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    e = sl[:, :8].to(torch.int32).repeat_interleave(32, dim=1)[:, :k]
+    out = torch.zeros(nch, S_CHUNK, dtype=torch.int32, device=sl.device)
+    out.scatter_(1, (ent & (S_CHUNK - 1)).to(torch.int64), _fp4_bits(ent >> 12, e))
     return out.view(torch.float32)
 
 
@@ -94,10 +109,14 @@ WRITE_BACKS = ("lazy", "sync", "deferred")
 OUTER_WIRES = ("f32", "bf16", "int8", "fp4", "topk")
 # The wires that send one fixed-size slot per tree chunk (q8_slot_plan; _all_reduce_q8): "int8"
 # (dl_q8.hip), "fp4" (dl_fp4.hip, OCP MX block-scaled E2M1) and "topk" (dl_topk.hip: the k
-# largest-magnitude entries of a chunk, 6k bytes). They share the slot plan, the exchange, its
+# largest-magnitude entries of a chunk, 6k bytes, or 16 + 2k with 4-bit values). They share the slot plan, the exchange, its
 # buffers and pipelining, and the residual arenas of error feedback.
 SLOT_WIRES = ("int8", "fp4", "topk")
 DEFAULT_TOPK = 64  # entries per chunk of the "topk" wire (DILOCO_OUTER_TOPK)
+# How the "topk" wire sends a selected value (DILOCO_OUTER_TOPK_VALUES): "f32", its own 32 bits
+# in a 6k-byte slot (dl_topk.hip), or "fp4", an E2M1 nibble beside the 12-bit position in one
+# u16, a scale byte per 32 entries, 16 + 2k bytes (dl_topk_fp4.hip)
+TOPK_VALUES = ("f32", "fp4")
 # The fp4 wire's randomised Hadamard rotation (dl_fp4_rot.hip; DILOCO_OUTER_FP4_ROTATE, off if
 # unset): the seed of its signs (DILOCO_OUTER_FP4_SEED) must be the same on every rank -- a peer
 # that decodes with another seed reads noise.
@@ -699,7 +718,7 @@ class DeviceOuterMirror:
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = False,
                  wire: str = "f32", exchange: str = "sharded", keep_params: bool = False,
                  error_feedback: bool = False, topk: int = DEFAULT_TOPK, rotate: bool = False,
-                 rot_seed: int = DEFAULT_FP4_SEED):
+                 rot_seed: int = DEFAULT_FP4_SEED, topk_values: str = "f32"):
         """keep_params: the outer model's Parameter objects stay the ones it has (their class
         switched to OuterParameter in place) -- for an outer model that got its device only
         at its first compute_pseudo_gradient, after get_optimizer took references to them.
@@ -727,6 +746,14 @@ class DeviceOuterMirror:
         if wire == "topk" and (self.topk % 8 or not _lib.TOPK_MIN_K <= self.topk <= _lib.TOPK_MAX_K):
             raise ValueError(f"topk {topk}: a multiple of 8 in [{_lib.TOPK_MIN_K}, "
                              f"{_lib.TOPK_MAX_K}]")
+        if topk_values not in TOPK_VALUES:
+            raise ValueError(f"topk_values {topk_values!r}: one of {TOPK_VALUES}")
+        if topk_values != "f32" and wire != "topk":
+            raise ValueError(f"topk_values={topk_values!r} is how the 'topk' wire sends a value; "
+                             f"the wire is {wire!r}")
+        # the "topk" wire's kernel set: the _topk methods, or their _topk_fp4 twins
+        self.topk_values = topk_values
+        self._tk = "topk_fp4" if topk_values == "fp4" else "topk"
         self._q8_res: Optional[torch.Tensor] = None
         self._q8_res_load: Optional[list] = None  # a loaded stage-2 state, until the buffers exist
         self.exchange = exchange
@@ -1347,7 +1374,8 @@ class DeviceOuterMirror:
     # _slot_reduce), the fused optimizer passes (_q8_sgd, _q8_adamw) and .grad's decode.
     def _slot_encode(self, b: int, slot: int, theta, residual, region) -> None:
         if self.wire == "topk":
-            self.k.delta_topk(self.tree, b, slot, theta, residual, self.topk, region)
+            getattr(self.k, "delta_" + self._tk)(self.tree, b, slot, theta, residual, self.topk,
+                                                 region)
         elif self.wire == "fp4" and self.rotate:
             self.k.delta_fp4_rot(self.tree, b, slot, theta, residual, self.rot_seed, region)
         elif self.wire == "fp4":
@@ -1359,7 +1387,7 @@ class DeviceOuterMirror:
 
     def _slot_reduce(self, recv, n: int, m: int, residual, red) -> None:
         if self.wire == "topk":
-            self.k.topk_reduce(recv, n, m, n, residual, self.topk, red)
+            getattr(self.k, self._tk + "_reduce")(recv, n, m, n, residual, self.topk, red)
         elif self.wire == "fp4":
             self.k.fp4_reduce(recv, n, m, n, residual, red)
         elif residual is not None:
@@ -1380,7 +1408,8 @@ class DeviceOuterMirror:
 
         S = FP4_SLOT if self.wire == "fp4" else Q8_SLOT  # the slot size is the codec's
         if self.wire == "topk":
-            S = _lib.TOPK_SLOT_BYTES(self.topk)
+            S = (_lib.TOPK_FP4_SLOT_BYTES if self.topk_values == "fp4"
+                 else _lib.TOPK_SLOT_BYTES)(self.topk)
         plan, base, rbase, mmax = q8_slot_plan(self.tree.bucket_chunks, n)
         z = dict(dtype=torch.uint8, device=self.device)
         segs = []
@@ -1537,7 +1566,7 @@ class DeviceOuterMirror:
                 continue
             sl = q["slots"][base * S:(base + nch) * S].view(nch, S)
             if self.wire == "topk":
-                g = _decode_topk(sl, self.topk)
+                g = (_decode_topk_fp4 if self.topk_values == "fp4" else _decode_topk)(sl, self.topk)
             elif self.wire == "fp4":
                 g = _decode_fp4(sl)
             else:
@@ -1562,9 +1591,9 @@ class DeviceOuterMirror:
             if works is not None:
                 works[b].wait()
             if self.wire == "topk":
-                self.k.unpack_sgd_topk(self.tree, b, self._q8_region(q, b), self.topk,
-                                       self.d_theta, mom, lr, momentum, nesterov, first,
-                                       SLOT_INNER if write else -1)
+                getattr(self.k, "unpack_sgd_" + self._tk)(
+                    self.tree, b, self._q8_region(q, b), self.topk, self.d_theta, mom, lr,
+                    momentum, nesterov, first, SLOT_INNER if write else -1)
                 continue
             if self.rotate:
                 self.k.unpack_sgd_fp4_rot(self.tree, b, self._q8_region(q, b), self.rot_seed,
@@ -1589,9 +1618,9 @@ class DeviceOuterMirror:
             if works is not None:
                 works[b].wait()
             if self.wire == "topk":
-                self.k.unpack_adamw_topk(self.tree, b, self._q8_region(q, b), self.topk,
-                                         self.d_theta, self.d_m1, self.d_m2, scalars,
-                                         SLOT_INNER if write else -1)
+                getattr(self.k, "unpack_adamw_" + self._tk)(
+                    self.tree, b, self._q8_region(q, b), self.topk, self.d_theta, self.d_m1,
+                    self.d_m2, scalars, SLOT_INNER if write else -1)
                 continue
             if self.rotate:
                 self.k.unpack_adamw_fp4_rot(self.tree, b, self._q8_region(q, b), self.rot_seed,
@@ -2024,7 +2053,7 @@ class LazyHostOuterMirror:
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = True,
                  wire: str = "f32", exchange: str = DEFAULT_EXCHANGE["host"],
                  error_feedback: bool = False, topk: int = DEFAULT_TOPK, rotate: bool = False,
-                 rot_seed: int = DEFAULT_FP4_SEED):
+                 rot_seed: int = DEFAULT_FP4_SEED, topk_values: str = "f32"):
         self.device = torch.device(device)
         params = module_params(outer_model)
         if not params:
@@ -2037,7 +2066,7 @@ class LazyHostOuterMirror:
                 for p in params])
         self.dev = DeviceOuterMirror(twin, self.device, kernels, bucket_cap_elems, fused, wire,
                                      exchange, error_feedback=error_feedback, topk=topk,
-                                     rotate=rotate, rot_seed=rot_seed)
+                                     rotate=rotate, rot_seed=rot_seed, topk_values=topk_values)
         self._twin = twin
         self.fused, self.wire, self.exchange = fused, wire, exchange
         from .utils import env_flag

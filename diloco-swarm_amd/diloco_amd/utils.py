@@ -82,7 +82,7 @@ from torch.optim import SGD, AdamW, Optimizer
 
 from .kernels import default_kernels
 from .mirror import (DEFAULT_EXCHANGE, DEFAULT_FP4_SEED, DEFAULT_TOPK, OUTER_EXCHANGES, OUTER_WIRES, SLOT_WIRES,
-                     WRITE_BACKS, DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
+                     TOPK_VALUES, WRITE_BACKS, DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
 from .optim import InnerAdamW, OuterAdamW, OuterSGD
 from . import _lib
 from ._lib import ALL_BUCKETS
@@ -98,6 +98,7 @@ _EXCHANGE = "_diloco_exchange"
 _EXCHANGE_ASKED = "_diloco_exchange_asked"  # by argument or DILOCO_OUTER_EXCHANGE
 _Q8_EF = "_diloco_q8_ef"  # int8 wire with error feedback (DILOCO_OUTER_Q8_EF)
 _TOPK = "_diloco_topk"  # entries per chunk of the "topk" wire (DILOCO_OUTER_TOPK)
+_TOPK_VALUES = "_diloco_topk_values"  # "fp4": the "topk" wire's 4-bit values (DILOCO_OUTER_TOPK_VALUES)
 _ROTATE = "_diloco_fp4_rotate"  # the fp4 wire's rotation seed when it is on, else None
 _ADAMW = "_diloco_adamw"  # an optim.OuterAdamW is attached
 OUTER_ADAMW = ("torch", "fused")
@@ -163,6 +164,8 @@ def outer_mirror(outer_model: nn.Module, device=None):
         ef = {"error_feedback": True} if getattr(outer_model, _Q8_EF, False) else {}
         if getattr(outer_model, _WIRE, "f32") == "topk":  # likewise named for its own wire only
             ef["topk"] = getattr(outer_model, _TOPK)
+            if getattr(outer_model, _TOPK_VALUES, "f32") != "f32":  # likewise
+                ef["topk_values"] = getattr(outer_model, _TOPK_VALUES)
         if getattr(outer_model, _ROTATE, None) is not None:  # likewise
             ef.update(rotate=True, rot_seed=getattr(outer_model, _ROTATE))
         if getattr(outer_model, _PLACEMENT, "host") == "device":
@@ -221,7 +224,7 @@ def _inner_device(inner_model: nn.Module) -> torch.device:
 def get_outer_model(inner_model: nn.Module, placement: str = None,
                     write_back: str = None, fused: bool = None, wire: str = None,
                     exchange: str = None, error_feedback: bool = None,
-                    topk: int = None, rotate: bool = None) -> nn.Module:
+                    topk: int = None, rotate: bool = None, topk_values: str = None) -> nn.Module:
     """Initializes the outer model from the inner model (src/utils.py:213-216).
 
     placement "host" (the reference's, default) or "device" (in HBM: on the inner model's GPU;
@@ -241,7 +244,11 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     every 4096-element chunk as exact fp32 values (dl_delta_topk, dl_topk_reduce,
     dl_unpack_sgd_topk / dl_unpack_adamw_topk); its error_feedback (None reads
     DILOCO_OUTER_TOPK_EF) is ON by default, for this wire only -- without it whatever was not
-    selected is lost -- and error_feedback=False is allowed. rotate (fp4 wire only; None reads
+    selected is lost -- and error_feedback=False is allowed. topk_values (topk wire only; None
+    reads DILOCO_OUTER_TOPK_VALUES, default "f32"): "fp4" sends each selected entry as one u16,
+    its 12-bit position beside an E2M1 nibble under a scale byte per 32 entries (16 + 2k bytes
+    per chunk instead of 6k; dl_delta_topk_fp4, dl_topk_fp4_reduce, dl_unpack_*_topk_fp4); the
+    selection is unchanged and the rounding error joins the residual. rotate (fp4 wire only; None reads
     DILOCO_OUTER_FP4_ROTATE, default off): every 256-element block is multiplied by random signs
     and Hadamard-transformed before the quantiser and transformed back after the decoder
     (dl_delta_fp4_rot, dl_unpack_*_fp4_rot, dl_decode_fp4_rot for .grad), which makes the
@@ -286,6 +293,13 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
                              f"{_lib.TOPK_MAX_K}]")
     elif topk is not None:
         raise ValueError(f"topk={topk} is the 'topk' wire's entries per chunk; the wire is {wire!r}")
+    if topk_values is None:  # consulted for its own wire only
+        topk_values = (os.environ.get("DILOCO_OUTER_TOPK_VALUES") or "f32") if wire == "topk" else "f32"
+    elif wire != "topk":
+        raise ValueError(f"topk_values={topk_values!r} is how the 'topk' wire sends a value; the "
+                         f"wire is {wire!r}")
+    if topk_values not in TOPK_VALUES:
+        raise ValueError(f"topk_values {topk_values!r}: one of {TOPK_VALUES}")
     if exchange is None:
         exchange = os.environ.get("DILOCO_OUTER_EXCHANGE") or None
     asked = exchange is not None
@@ -321,6 +335,7 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     object.__setattr__(outer_model, _WIRE, wire)
     object.__setattr__(outer_model, _Q8_EF, bool(error_feedback))
     object.__setattr__(outer_model, _TOPK, topk)
+    object.__setattr__(outer_model, _TOPK_VALUES, topk_values)
     object.__setattr__(outer_model, _ROTATE, seed)
     object.__setattr__(outer_model, _EXCHANGE, exchange)
     object.__setattr__(outer_model, _EXCHANGE_ASKED, asked)

@@ -41,6 +41,8 @@ extern "C" {
 #define DL_TOPK_MIN_K 8
 #define DL_TOPK_MAX_K 256
 #define DL_TOPK_SLOT_BYTES(k) (6 * (k))
+/* top-k wire with 4-bit values: 8 scale bytes, 8 zero bytes, k u16 entries (index | nibble << 12) */
+#define DL_TOPK_FP4_SLOT_BYTES(k) (16 + 2 * (k))
 
 /* wire / packed dtypes */
 #define DL_F32 0
@@ -701,6 +703,61 @@ DL_API int dl_unpack_adamw_topk(dl_tree_t tree, int32_t bucket, const void* slot
                                 float* exp_avg_sq_packed, float decay, float w1, float beta2,
                                 float w2, float neg_step_size, float bc2_sqrt, float eps,
                                 int32_t inner_slot, dl_stream_t stream);
+
+/* ---- top-k wire with 4-bit (E2M1) values (not in the reference) ----------------------------
+ * The top-k wire above with each sent entry in ONE u16: a position in a chunk needs 12 bits
+ * (DL_CHUNK_ELEMS == 4096), an E2M1 code with its sign 4. k as above (a multiple of 8 in
+ * [DL_TOPK_MIN_K, DL_TOPK_MAX_K], else DL_E_ARG and dl_last_error() names k). One
+ * DL_TOPK_FP4_SLOT_BYTES(k) = (16 + 2k)-byte slot per chunk, in chunk order (a multiple of 16 B):
+ *   bytes [0, 8)        one E8M0 scale byte per ENTRY GROUP: group g is entries
+ *                       [32g, 32g + 32) ∩ [0, k) of the slot, in slot order; 0 for a group
+ *                       with no entry
+ *   bytes [8, 16)       zero
+ *   bytes [16, 16 + 2k) k u16 entries, entry e = index | nibble << 12, indices strictly ascending
+ * (16 + 2k)/4096 B/param: 0.035 at k = 64.
+ * Which positions are sent: select_k of the top-k wire, unchanged, on the exact fp32 values;
+ * quantisation comes after it and never changes the set.
+ * How they are sent, with fp4_scale / fp4_nibble / fp4_value the fp4 wire's rules above:
+ *   per entry group  A = the largest key of its entries; E = fp4_scale(A): the smallest power
+ *                    of two that keeps A on the grid (nothing saturates); a denormal or zero A
+ *                    gives E = 0, a non-finite A gives E = 255
+ *   per entry        nibble = fp4_nibble(value, 2^(127 - E)): nearest, ties to the even code, no
+ *                    sign on code 0 (every nibble of an E = 255 group is 0)
+ * Decode: a dense chunk of +0 with fp4_value(nibble, E_group) = ±grid[code]·2^(E - 127) at each
+ * index; exact; an E = 255 group decodes to NaN. A slot of all zero bytes decodes to zeros; the
+ * reduce of all-zero input writes entries e | 0 << 12 under scale 0. A selected element below a
+ * quarter of its group's step is sent as code 0, which is valid: it stays whole in the residual.
+ * Residual, where given: r[i] <- x_i - deq_i for a selected position (one rounded fp32
+ * subtract, as on the fp4 wire), r[i] <- x_i otherwise; inside the chunk only, in place, by the
+ * lane that read it. No special cases: a non-finite selected element makes its group's residual
+ * entries NaN by IEEE rules, as on the fp4 wire.
+ * dl_delta_topk_fp4: x as dl_delta_topk; slot(c) <- the above; every byte of every launched slot
+ * is written and no byte of any other slot; nothing of θ, inner or r is touched past a chunk's
+ * length; results do not depend on alignment, the grid or the bucket split.
+ * 8 + (16 + 2k)/4096 B/param (16.035 with the residual at k = 64).
+ * dl_topk_fp4_reduce: acc as dl_topk_reduce with each entry decoded (one rounded add per entry,
+ * peers in rank order), / divisor if > 1, + r2; then selected, quantised and the residual
+ * written as above over all DL_CHUNK_ELEMS positions. out may alias recv only at n_peers == 1.
+ * Every peer receives byte-identical slots.
+ * dl_unpack_sgd_topk_fp4 / dl_unpack_adamw_topk_fp4: g = decode(slot), then as the _topk entry
+ * points: bit-identical to decoding into an fp32 wire and running dl_unpack_sgd /
+ * dl_unpack_adamw (divisor 1). 20.035 / 28.035 B/param at k = 64.
+ * Arguments and their checks are the top-k entry points'. */
+DL_API int dl_delta_topk_fp4(dl_tree_t tree, int32_t bucket, int32_t inner_slot,
+                             const float* outer_packed, float* residual_packed /* NULL: none */,
+                             int32_t k, void* slots, dl_stream_t stream);
+DL_API int dl_topk_fp4_reduce(const void* recv, int32_t n_peers, int32_t n_slots, int32_t divisor,
+                              float* residual /* NULL: none */, int32_t k, void* out,
+                              dl_stream_t stream);
+DL_API int dl_unpack_sgd_topk_fp4(dl_tree_t tree, int32_t bucket, const void* slots, int32_t k,
+                                  float* outer_packed, float* mom_packed, float lr, float momentum,
+                                  int32_t nesterov, int32_t first_step, int32_t inner_slot,
+                                  dl_stream_t stream);
+DL_API int dl_unpack_adamw_topk_fp4(dl_tree_t tree, int32_t bucket, const void* slots, int32_t k,
+                                    float* outer_packed, float* exp_avg_packed,
+                                    float* exp_avg_sq_packed, float decay, float w1, float beta2,
+                                    float w2, float neg_step_size, float bc2_sqrt, float eps,
+                                    int32_t inner_slot, dl_stream_t stream);
 
 /* ---- serializer (src/serializer.py:11-15) ----------------------------------------------
  * out is fp32 of 2*numel elements: out[0] = meta0, out[1] = meta1, out[numel + i] =

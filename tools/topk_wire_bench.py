@@ -19,7 +19,13 @@ should not exceed the fp4 counterpart's median by more than that counterpart's o
 over the rounds. A pair that misses is reported as missing, with the ratio; nothing is tuned
 here.
 
+--values fp4: the top-k wire's 4-bit-value kernels (dl_delta_topk_fp4, dl_topk_fp4_reduce,
+dl_unpack_*_topk_fp4; 16 + 2k-byte slots) beside their exact-value counterparts above instead,
+same method; the bar is the same with the exact-value kernel as the counterpart (the traffic is
+the same to within 0.06 B/param).
+
     python tools/topk_wire_bench.py [--tree t125] [--rounds 9] [--out profiles/topk_wire_t125.json]
+    python tools/topk_wire_bench.py --values fp4 --out profiles/topk_fp4_wire_t125.json
 """
 import argparse
 import json
@@ -37,6 +43,8 @@ STEP_TIMEOUT_S = 300
 PAIRS = (("dl_delta_topk", "dl_delta_fp4"), ("dl_delta_topk_residual", "dl_delta_fp4_residual"),
          ("dl_topk_reduce", "dl_fp4_reduce"), ("dl_topk_reduce_residual", "dl_fp4_reduce_residual"),
          ("dl_unpack_sgd_topk", "dl_unpack_sgd_fp4"), ("dl_unpack_adamw_topk", "dl_unpack_adamw_fp4"))
+# --values fp4: the same six with the 4-bit-value kernel first and the exact-value one as counterpart
+FP4_PAIRS = tuple((a.replace("topk", "topk_fp4"), a) for a, _ in PAIRS)
 
 
 def step_kernels(args):
@@ -69,14 +77,18 @@ def step_kernels(args):
     resid2 = torch.zeros(m * C, **z)
     sgd = (0.7, 0.9, True, False, SLOT_INNER)
     runs = {}
-    for tag, S in (("topk", _lib.TOPK_SLOT_BYTES(TOPK)), ("fp4", FP4_SLOT)):
+    pairs = FP4_PAIRS if args.values == "fp4" else PAIRS
+    other = ("topk_fp4", _lib.TOPK_FP4_SLOT_BYTES(TOPK)) if args.values == "fp4" else ("fp4", FP4_SLOT)
+    for tag, S in (("topk", _lib.TOPK_SLOT_BYTES(TOPK)), other):
         slots = torch.zeros(tree.n_chunks * S, dtype=torch.uint8, device=dev)
-        if tag == "topk":
-            enc = lambda r, s=slots: k.delta_topk(tree, all_, SLOT_INNER, theta, r, TOPK, s)  # noqa: E731
-            red_ = lambda r, a, o: k.topk_reduce(a, 2, m, 2, r, TOPK, o)  # noqa: E731
-            usgd = lambda a: k.unpack_sgd_topk(tree, all_, a, TOPK, theta, mom, *sgd)  # noqa: E731
-            uadam = lambda a: k.unpack_adamw_topk(tree, all_, a, TOPK, theta, m1, m2, adam,  # noqa: E731
-                                                  SLOT_INNER)
+        if tag != "fp4":  # the two top-k kernel sets take the same arguments
+            f = {n: getattr(k, n.replace("topk", tag)) for n in
+                 ("delta_topk", "topk_reduce", "unpack_sgd_topk", "unpack_adamw_topk")}
+            enc = lambda r, s=slots, f=f: f["delta_topk"](tree, all_, SLOT_INNER, theta, r, TOPK, s)  # noqa: E731
+            red_ = lambda r, a, o, f=f: f["topk_reduce"](a, 2, m, 2, r, TOPK, o)  # noqa: E731
+            usgd = lambda a, f=f: f["unpack_sgd_topk"](tree, all_, a, TOPK, theta, mom, *sgd)  # noqa: E731
+            uadam = lambda a, f=f: f["unpack_adamw_topk"](tree, all_, a, TOPK, theta, m1, m2, adam,  # noqa: E731
+                                                          SLOT_INNER)
         else:
             enc = lambda r, s=slots: k.delta_fp4(tree, all_, SLOT_INNER, theta, r, s)  # noqa: E731
             red_ = lambda r, a, o: k.fp4_reduce(a, 2, m, 2, r, o)  # noqa: E731
@@ -95,7 +107,7 @@ def step_kernels(args):
                                           rbytes + 8 * m * C),
             f"dl_unpack_sgd_{tag}": (lambda f=usgd, a=avg: f(a), wire + 20 * elems),
             f"dl_unpack_adamw_{tag}": (lambda f=uadam, a=avg: f(a), wire + 28 * elems)})
-    order = [n for pair in PAIRS for n in pair]  # counterparts are neighbours in a round
+    order = [n for pair in pairs for n in pair]  # counterparts are neighbours in a round
     res = _measure({n: runs[n] for n in order}, args.rounds)
     tree.close()
     return {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "k": TOPK,
@@ -106,6 +118,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--tree", default="t125")
+    ap.add_argument("--values", choices=("f32", "fp4"), default="f32",
+                    help="fp4: the 4-bit-value kernels beside the exact-value ones")
     ap.add_argument("--out", default=None)
     ap.add_argument("--step-out", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -119,12 +133,12 @@ def main():
         return
     part = os.path.join(tempfile.mkdtemp(prefix="dl_topk_bench_"), "kernels.json")
     subprocess.run([sys.executable, os.path.abspath(__file__), "--tree", args.tree,
-                    "--rounds", str(args.rounds), "--step-out", part],
+                    "--rounds", str(args.rounds), "--values", args.values, "--step-out", part],
                    check=True, timeout=STEP_TIMEOUT_S)
     with open(part) as f:
         res = json.load(f)
     kn, bar = res["kernels"], {}
-    for new, old in PAIRS:
+    for new, old in (FP4_PAIRS if args.values == "fp4" else PAIRS):
         a, b = kn[new], kn[old]
         bar[new] = {"counterpart": old, "median_ms": a["median_ms"],
                     "counterpart_median_ms": b["median_ms"],
@@ -134,8 +148,9 @@ def main():
                     "meets_bar": bool(a["median_ms"] <= b["median_ms"] + b["max_minus_min_ms"])}
     out = {"tool": "tools/topk_wire_bench.py", "tree": args.tree, "rounds": args.rounds,
            "cold": "a 1 GiB copy through other memory before every timed launch",
-           "bar": "median <= the fp4 counterpart's median + the counterpart's own max - min, "
-                  "same run",
+           "values": args.values,
+           "bar": "median <= the counterpart's median + the counterpart's own max - min, same run "
+                  "(counterpart: the fp4 wire's kernel; --values fp4: the exact-value top-k kernel)",
            "not_measured": ["any multi-GPU run", "any rate of the outer step at N > 1",
                             "the effect of k or of the sparse wire on a training run's loss"],
            **res, "pairs": bar, "all_meet_bar": all(v["meets_bar"] for v in bar.values())}
