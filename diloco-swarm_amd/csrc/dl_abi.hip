@@ -1442,6 +1442,59 @@ DL_API int dl_unpack_avg_fp4(dl_tree_t t, int32_t b, const void* slots, int32_t 
                          : hip_fail(e, "dl_unpack_avg_fp4");
 }
 
+// The gradient side of the top-k exchanges (dl_topk_grad.hip): the fp4 pair's checks, launches
+// and policies after the check of k; one body per call for both value formats, as for the
+// outer step's top-k calls.
+}  // extern "C"
+
+namespace {
+
+int gather_topk(const char* who, decltype(&dl::launch_gather_topk) launch, dl_tree_t t, int32_t b,
+                int32_t src_slot, float* residual, int32_t k, void* slots, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_topk_k(k, who));
+  if (residual) DL_TRY(check_packed(residual, who, "residual"));
+  DL_TRY(check_packed(slots, who, "slots"));
+  DL_TRY(make_launch(t, b, s, &L, who, kAutoDeltaQ8));
+  DL_TRY(check_slot(t, src_slot, who));
+  DL_TRY(slot_begin(t, src_slot, L.stream, who));
+  hipError_t e = launch(L, src_slot, residual, k, static_cast<uint8_t*>(slots));
+  return e == hipSuccess ? slot_end(t, src_slot, L.stream, who) : hip_fail(e, who);
+}
+
+int unpack_avg_topk(const char* who, decltype(&dl::launch_unpack_avg_topk) launch, dl_tree_t t,
+                    int32_t b, const void* slots, int32_t k, int32_t dst_slot, double* partials,
+                    dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_topk_k(k, who));
+  DL_TRY(check_packed(slots, who, "slots"));
+  if (partials) DL_TRY(check_partials(partials, who));
+  DL_TRY(make_launch(t, b, s, &L, who, kAutoNT, Big::two_chunks));
+  DL_TRY(check_slot(t, dst_slot, who));
+  DL_TRY(slot_begin(t, dst_slot, L.stream, who));
+  hipError_t e = launch(L, static_cast<const uint8_t*>(slots), k, dst_slot, partials);
+  return e == hipSuccess ? slot_end(t, dst_slot, L.stream, who) : hip_fail(e, who);
+}
+
+}  // namespace
+
+extern "C" {
+
+#define DL_TOPK_GRAD_ENTRY_POINTS(SFX)                                                             \
+  DL_API int dl_gather_topk##SFX(dl_tree_t t, int32_t b, int32_t src_slot, float* residual,        \
+                                 int32_t k, void* slots, dl_stream_t s) {                          \
+    return gather_topk("dl_gather_topk" #SFX, dl::launch_gather_topk##SFX, t, b, src_slot,         \
+                       residual, k, slots, s);                                                     \
+  }                                                                                                \
+  DL_API int dl_unpack_avg_topk##SFX(dl_tree_t t, int32_t b, const void* slots, int32_t k,         \
+                                     int32_t dst_slot, double* partials, dl_stream_t s) {          \
+    return unpack_avg_topk("dl_unpack_avg_topk" #SFX, dl::launch_unpack_avg_topk##SFX, t, b,       \
+                           slots, k, dst_slot, partials, s);                                       \
+  }
+DL_TOPK_GRAD_ENTRY_POINTS()
+DL_TOPK_GRAD_ENTRY_POINTS(_fp4)
+#undef DL_TOPK_GRAD_ENTRY_POINTS
+
 DL_API int dl_norm_finish(const double* partials, int32_t n_partials, float max_norm, float* out2,
                           dl_stream_t s) {
   if (n_partials < 0) return fail(DL_E_ARG, "dl_norm_finish: n_partials %d", n_partials);

@@ -159,6 +159,15 @@ hipError_t launch_unpack_adamw_topk_fp4(const Launch& L, const uint8_t* slots, i
 hipError_t launch_gather_fp4(const Launch& L, int src_slot, float* resid, uint8_t* slots);
 hipError_t launch_unpack_avg_fp4(const Launch& L, const uint8_t* slots, int dst_slot,
                                  double* partials);
+// the gradient side of the top-k exchanges (dl_topk_grad.hip): the same pair on the 6k-byte and
+// the (16 + 2k)-byte slots (the caller checked k)
+hipError_t launch_gather_topk(const Launch& L, int src_slot, float* resid, int k, uint8_t* slots);
+hipError_t launch_gather_topk_fp4(const Launch& L, int src_slot, float* resid, int k,
+                                  uint8_t* slots);
+hipError_t launch_unpack_avg_topk(const Launch& L, const uint8_t* slots, int k, int dst_slot,
+                                  double* partials);
+hipError_t launch_unpack_avg_topk_fp4(const Launch& L, const uint8_t* slots, int k, int dst_slot,
+                                      double* partials);
 hipError_t launch_unpack_adamw(const Launch& L, const void* wire, int wire_dtype, int divisor,
                                float* outer, float* m1, float* m2, AdamArgs a, int inner_slot);
 hipError_t launch_delta_pack_adamw(const Launch& L, int inner_slot, float* outer, void* wire,

@@ -159,12 +159,20 @@ DP_EXCHANGE = os.environ.get("DILOCO_DP_EXCHANGE", "rccl")
 # 8(n-1)/n, with DP_Q8_EF (consulted for int8 only, off if unset) both quantisers' error feedback;
 # or "fp4" -- the outer step's MXFP4 codec there, 2(n-1)/n * 0.531 bus bytes per parameter, with
 # DP_FP4_EF (DILOCO_DP_FP4_EF; consulted for fp4 only, off if unset). No torch dtype names the
-# fp4 format on every build, so GradSync takes the string
-DP_WIRES = {"f32": torch.float32, "bf16": torch.bfloat16, "int8": torch.int8, "fp4": "fp4"}
+# fp4 format on every build, so GradSync takes the string; or "topk" -- the outer step's top-k
+# sparse wire there: DP_TOPK entries per 4096-element chunk (DILOCO_DP_TOPK, default 64), sent as
+# DP_TOPK_VALUES (DILOCO_DP_TOPK_VALUES: "f32", 6k bytes per chunk, or "fp4", 16 + 2k), 2(n-1)/n *
+# 0.094 (0.035) bus bytes per parameter at k = 64, with DP_TOPK_EF (DILOCO_DP_TOPK_EF, ON if
+# unset: without it what selection leaves out is lost). The three are consulted for topk only
+DP_WIRES = {"f32": torch.float32, "bf16": torch.bfloat16, "int8": torch.int8, "fp4": "fp4",
+            "topk": "topk"}
 DP_WIRE = os.environ.get("DILOCO_DP_WIRE", "f32")
 _ON = ("1", "true", "yes", "on")
 DP_Q8_EF = os.environ.get("DILOCO_DP_Q8_EF", "0").strip().lower() in _ON
 DP_FP4_EF = os.environ.get("DILOCO_DP_FP4_EF", "0").strip().lower() in _ON
+DP_TOPK = int(os.environ.get("DILOCO_DP_TOPK") or 64)
+DP_TOPK_VALUES = os.environ.get("DILOCO_DP_TOPK_VALUES") or "f32"
+DP_TOPK_EF = os.environ.get("DILOCO_DP_TOPK_EF", "1").strip().lower() in _ON
 
 
 def dp_wire():
@@ -172,8 +180,16 @@ def dp_wire():
     wire's own error-feedback knob (DP_Q8_EF for int8, DP_FP4_EF for fp4)."""
     if DP_WIRE not in DP_WIRES:
         raise ValueError(f"DILOCO_DP_WIRE {DP_WIRE!r}: one of {tuple(DP_WIRES)}")
-    ef = {"int8": DP_Q8_EF, "fp4": DP_FP4_EF}.get(DP_WIRE, False)
+    ef = {"int8": DP_Q8_EF, "fp4": DP_FP4_EF, "topk": DP_TOPK_EF}.get(DP_WIRE, False)
     return DP_WIRES[DP_WIRE], bool(ef)
+
+
+def dp_topk() -> dict:
+    """GradSync's topk / topk_values arguments: DP_TOPK and DP_TOPK_VALUES on the topk wire,
+    nothing on any other (GradSync rejects them there)."""
+    if DP_WIRE != "topk":
+        return {}
+    return {"topk": int(DP_TOPK), "topk_values": DP_TOPK_VALUES}
 
 
 class DPSync:
@@ -249,7 +265,7 @@ class DPSync:
         if gs is None or not gs.matches(params):
             wire, ef = dp_wire()
             gs = GradSync(params, self.dp_group(params[0].device), num_peers, wire_dtype=wire,
-                          exchange=DP_EXCHANGE, error_feedback=ef)
+                          exchange=DP_EXCHANGE, error_feedback=ef, **dp_topk())
             self._grad_syncs[id(model)] = gs
         return gs.sync(max_norm)
 

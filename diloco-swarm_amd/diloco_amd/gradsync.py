@@ -38,11 +38,22 @@ load_q8_ef_state serve both slot wires). One replica: encode, dl_fp4_reduce of t
 itself (the identity: deq(enc(deq(s))) == deq(s)), decode. The two slot wires differ in their
 slot size and their three calls only (SLOT_WIRES).
 
+wire_dtype="topk": the outer step's top-k sparse wire on the per-step exchange -- per chunk the
+topk (default 64) entries of largest magnitude, as exact fp32 values (topk_values="f32", 6k-byte
+slots) or as E2M1 nibbles packed with their 12-bit positions (topk_values="fp4", 16 + 2k bytes):
+per bucket dl_gather_topk[_fp4] -> all_to_all -> dl_topk[_fp4]_reduce (divisor n) -> all_gather
+-> dl_unpack_avg_topk[_fp4]: 2(n-1)/n · 0.094 (0.035) bus bytes per parameter at k = 64.
+error_feedback=None means ON for this wire only (what selection leaves out -- 98 % of the
+elements at k = 64 -- stays in the residual and competes again next step; off, it is lost);
+explicit False turns it off. The arenas, q8_ef_state / load_q8_ef_state and the one-replica path
+are the other slot wires'. The selection, tie and residual rules are include/diloco_hip.h's.
+
 sync(max_norm): the clip_grad_norm_ that follows the sync in the training loop
 (src/train.py:255), fused into it. Every dl_unpack_avg becomes dl_unpack_avg_sumsq, which holds
 each averaged gradient in registers on its way to .grad and leaves the chunk's Σ g²; after the
 last bucket dl_norm_finish and one dl_scale_by run on the same stream (int8 wire:
-dl_unpack_avg_q8, fp4 wire: dl_unpack_avg_fp4 leave the same partial sums). Equal, bit for bit, to
+dl_unpack_avg_q8, fp4 wire: dl_unpack_avg_fp4, top-k wire: dl_unpack_avg_topk[_fp4] leave the
+same partial sums). Equal, bit for bit, to
 sync() followed by utils.clip_grad_norm_, without that call's read of every gradient.
 """
 from __future__ import annotations
@@ -54,20 +65,30 @@ import torch.distributed as dist
 
 from .kernels import FP4_SLOT, Q8_SLOT, default_kernels
 from . import _lib
+from .mirror import DEFAULT_TOPK, TOPK_VALUES
 from .outer import _Done, pipelined_buckets
 from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_GRAD, q8_slot_plan
 
 
 # The slot wires: wire_dtype -> slot bytes. Each has a three-call codec (encode, reduce, decode;
-# GradSync._codec), as the mirror's SLOT_WIRES; everything between the calls is shared.
+# GradSync._codec), as the mirror's SLOT_WIRES; everything between the calls is shared. The
+# top-k wire's slot depends on k and on how a value is sent: slot_wire_bytes.
 SLOT_WIRES = {torch.int8: Q8_SLOT, "fp4": FP4_SLOT}
+
+
+def slot_wire_bytes(wire_dtype, topk: Optional[int] = None, topk_values: str = "f32"):
+    """Bytes of one chunk's slot on `wire_dtype`; None on the flat wires (f32, bf16)."""
+    if wire_dtype == "topk":
+        return (_lib.TOPK_FP4_SLOT_BYTES if topk_values == "fp4" else _lib.TOPK_SLOT_BYTES)(topk)
+    return SLOT_WIRES.get(wire_dtype)
 
 
 class GradSync:
     def __init__(self, params: Sequence[torch.Tensor], group: Optional[dist.ProcessGroup],
                  world_size: int, wire_dtype=torch.float32,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, kernels=None,
-                 exchange: str = "rccl", error_feedback: bool = False):
+                 exchange: str = "rccl", error_feedback: Optional[bool] = None,
+                 topk: Optional[int] = None, topk_values: Optional[str] = None):
         self.params = list(params)
         self.k = kernels or default_kernels()
         self.device = self.params[0].device
@@ -75,20 +96,43 @@ class GradSync:
         if exchange not in ("rccl", "a2a"):
             raise ValueError(f"exchange {exchange!r}: 'rccl' or 'a2a'")
         self.a2a = exchange == "a2a"
-        if isinstance(wire_dtype, str) and wire_dtype != "fp4":
-            raise ValueError(f"wire_dtype {wire_dtype!r}: a torch dtype or 'fp4'")
+        if isinstance(wire_dtype, str) and wire_dtype not in ("fp4", "topk"):
+            raise ValueError(f"wire_dtype {wire_dtype!r}: a torch dtype, 'fp4' or 'topk'")
         self.q8 = wire_dtype == torch.int8
         self.fp4 = wire_dtype == "fp4"
-        # a slot wire (int8, fp4): the bytes of one chunk's slot; None on the flat wires
-        self.slot_bytes = SLOT_WIRES.get(wire_dtype)
-        # slot wires only: carry what each quantiser rounds away into the next sync
-        # (dl_gather_q8_ef, dl_q8_reduce_ef; dl_gather_fp4 / dl_fp4_reduce with a residual)
-        self.error_feedback = bool(error_feedback)
+        self.topk_wire = wire_dtype == "topk"
+        if self.topk_wire:
+            if topk is None:
+                topk = DEFAULT_TOPK
+            if topk % 8 or not _lib.TOPK_MIN_K <= topk <= _lib.TOPK_MAX_K:
+                raise ValueError(f"topk {topk}: a multiple of 8 in [{_lib.TOPK_MIN_K}, "
+                                 f"{_lib.TOPK_MAX_K}]")
+        elif topk is not None:
+            raise ValueError(f"topk={topk} is the 'topk' wire's entries per chunk; the wire is "
+                             f"{wire_dtype!r}")
+        if topk_values is None:
+            topk_values = "f32"
+        elif not self.topk_wire:
+            raise ValueError(f"topk_values={topk_values!r} is how the 'topk' wire sends a value; "
+                             f"the wire is {wire_dtype!r}")
+        if topk_values not in TOPK_VALUES:
+            raise ValueError(f"topk_values {topk_values!r}: one of {TOPK_VALUES}")
+        # the top-k wire only: entries per chunk, and "f32" or "fp4" values
+        self.topk = int(topk) if self.topk_wire else None
+        self.topk_values = topk_values if self.topk_wire else None
+        # a slot wire (int8, fp4, topk): the bytes of one chunk's slot; None on the flat wires
+        self.slot_bytes = slot_wire_bytes(wire_dtype, topk, topk_values)
+        # slot wires only: carry what each quantiser rounds away (the top-k wire: what selection
+        # leaves out) into the next sync (dl_gather_q8_ef, dl_q8_reduce_ef; dl_gather_fp4 /
+        # dl_fp4_reduce, dl_gather_topk / dl_topk_reduce and their _fp4 twins with a residual).
+        # None: on for the top-k wire, as on the outer step's, off for every other wire
+        self.error_feedback = self.topk_wire if error_feedback is None else bool(error_feedback)
         if self.error_feedback and self.slot_bytes is None:
             raise ValueError("error_feedback compensates the int8 / fp4 wire's quantiser; it "
                              "needs wire_dtype=torch.int8 or 'fp4'")
         if self.slot_bytes is not None and self.a2a:
-            raise ValueError(f"the {'fp4' if self.fp4 else 'int8'} wire has its own rank-order "
+            name = "topk" if self.topk_wire else "fp4" if self.fp4 else "int8"
+            raise ValueError(f"the {name} wire has its own rank-order "
                              "exchange; exchange='a2a' averages the fp32 grads")
         if dist.is_initialized() and self.world_size > 1:
             gs = dist.get_world_size(group)
@@ -292,6 +336,15 @@ class GradSync:
         slot wire; residual None: the call without error feedback."""
         k, tree = self.k, self.tree
         resid = self.q_residual  # None without error feedback
+        if self.topk_wire:
+            kk, q4 = self.topk, self.topk_values == "fp4"
+            gather = k.gather_topk_fp4 if q4 else k.gather_topk
+            red = k.topk_fp4_reduce if q4 else k.topk_reduce
+            unpack = k.unpack_avg_topk_fp4 if q4 else k.unpack_avg_topk
+            return (lambda b: gather(tree, b, SLOT_GRAD, resid, kk, self.q8_region(b)),
+                    lambda recv, n, m, divisor, residual, out: red(recv, n, m, divisor, residual,
+                                                                   kk, out),
+                    lambda b, p: unpack(tree, b, self.q8_region(b), kk, SLOT_GRAD, p))
         if self.fp4:
             return (lambda b: k.gather_fp4(tree, b, SLOT_GRAD, resid, self.q8_region(b)),
                     k.fp4_reduce,
@@ -314,7 +367,7 @@ class GradSync:
 
     def _sync_slots(self, clip=None) -> None:
         """encode(b) -> all_to_all(b) | reduce(b) -> all_gather(b) | decode(b) with the wire's
-        three calls (_codec: gather_q8 / q8_reduce / unpack_avg_q8, or their fp4 twins),
+        three calls (_codec: gather_q8 / q8_reduce / unpack_avg_q8, their fp4 or top-k twins),
         overlapped across buckets like _sync_a2a; the landing and reduce buffers alternate, so
         the bytes do not depend on the overlap."""
         n, nb, S = self.world_size, self.tree.n_buckets, self.slot_bytes

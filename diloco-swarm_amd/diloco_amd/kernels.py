@@ -387,6 +387,30 @@ class HipKernels:
         _lib.call("dl_unpack_avg_fp4", tree.handle, bucket, slots.data_ptr(), int(dst_slot),
                   _ptr(partials), _s(slots))
 
+    # the gradient side of the two top-k exchanges (dl_topk_grad.hip). residual None: no error
+    # feedback
+    def gather_topk(self, tree, bucket, src_slot, residual, k, slots) -> None:
+        """slots <- the k largest-magnitude entries of x per chunk, x = the gradients bound to
+        src_slot (+ residual); residual <- x with +0 at the selected positions, in place."""
+        _lib.call("dl_gather_topk", tree.handle, bucket, int(src_slot), _ptr(residual), int(k),
+                  slots.data_ptr(), _s(slots))
+
+    def gather_topk_fp4(self, tree, bucket, src_slot, residual, k, slots) -> None:
+        """gather_topk with the entries quantised per group of 32; residual <- x - deq at the
+        selected positions, x elsewhere."""
+        _lib.call("dl_gather_topk_fp4", tree.handle, bucket, int(src_slot), _ptr(residual),
+                  int(k), slots.data_ptr(), _s(slots))
+
+    def unpack_avg_topk(self, tree, bucket, slots, k, dst_slot, partials=None) -> None:
+        """dst_slot <- decode of the averaged slots (+0 but at the k positions); with partials
+        also the per-chunk Σ of the stored values² (grad_sumsq's, for norm_finish)."""
+        _lib.call("dl_unpack_avg_topk", tree.handle, bucket, slots.data_ptr(), int(k),
+                  int(dst_slot), _ptr(partials), _s(slots))
+
+    def unpack_avg_topk_fp4(self, tree, bucket, slots, k, dst_slot, partials=None) -> None:
+        _lib.call("dl_unpack_avg_topk_fp4", tree.handle, bucket, slots.data_ptr(), int(k),
+                  int(dst_slot), _ptr(partials), _s(slots))
+
     def unpack_avg(self, tree, bucket, wire, divisor, dst_slot, dst_packed=None) -> None:
         _lib.call("dl_unpack_avg", tree.handle, bucket, wire.data_ptr(), wire_code(wire.dtype),
                   int(divisor), int(dst_slot), _ptr(dst_packed), _s(wire))

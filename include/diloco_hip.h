@@ -759,6 +759,50 @@ DL_API int dl_unpack_adamw_topk_fp4(dl_tree_t tree, int32_t bucket, const void* 
                                     float w2, float neg_step_size, float bc2_sqrt, float eps,
                                     int32_t inner_slot, dl_stream_t stream);
 
+/* ---- the gradient side of the two top-k wires (not in the reference) -----------------------
+ * The per-step DP gradient average on the top-k slots: dl_gather_fp4 / dl_unpack_avg_fp4 with the
+ * slot formats, select_k, the quantiser and the residual rules of the two sections above;
+ * dl_topk_reduce / dl_topk_fp4_reduce with divisor n stand between the two. k as above (a
+ * multiple of 8 in [DL_TOPK_MIN_K, DL_TOPK_MAX_K], else DL_E_ARG and dl_last_error() names k).
+ * dl_gather_topk / dl_gather_topk_fp4, per chunk c of the bucket, g = slot src_slot (per-tensor
+ * fp32), j the element of the packed space:
+ *   x = g[seg][i]          (residual_packed NULL)
+ *   x = g[seg][i] + r[j]   (r = residual_packed: one rounded fp32 add)
+ *   slot(c) <- select_k(x), the _fp4 form quantised per entry group
+ *   r[j] <- +0 where selected (_fp4: x - deq), x elsewhere; in place, by the lane that read it
+ * byte for byte what dl_delta_topk / dl_delta_topk_fp4 write for outer = g, inner = +0
+ * (x - (+0) = x bit for bit, -0 included). Every byte of every launched slot is written,
+ * whatever it held before, and no byte of any other slot; of g and r nothing is loaded or
+ * stored past a chunk's length (the residual's padding is never written). Results do not depend
+ * on the gradient tensors' alignment, the grid or the bucket split. 4 + 6k/4096 B/param (12 +
+ * 6k/4096 with the residual: 8 read, 4 written); (16 + 2k)/4096 in place of 6k/4096 for _fp4.
+ * dl_unpack_avg_topk / dl_unpack_avg_topk_fp4, per chunk c of the bucket, dst = slot dst_slot
+ * (per-tensor fp32):
+ *   dst[seg][i] = decode(slot(c))[i]   (+0 everywhere but value[e] at index[e]; a slot of all
+ *                                       zero bytes decodes to zeros; a slot whose indices repeat,
+ *                                       other than that one, is not a valid slot)
+ *   partials[c] = Σ of the squares of the values stored to chunk c, when partials is not NULL:
+ *                 fp64, in dl_grad_sumsq's order over every element of the chunk (the zeros
+ *                 too), bit-identical to dl_grad_sumsq on dst afterwards; written for exactly
+ *                 the bucket's chunk range (n_chunk doubles, 8-B aligned)
+ * The slots are only read; an index is taken modulo DL_CHUNK_ELEMS; nothing is stored past a
+ * tensor's length; results do not depend on alignment, the grid or the bucket split.
+ * 4 + 6k/4096 B/param (4 + (16 + 2k)/4096 for _fp4), all but the slot bytes stores.
+ * slots non-null and 16-B aligned, a given residual 16-B aligned, partials 8-B aligned; the
+ * slot bound. */
+DL_API int dl_gather_topk(dl_tree_t tree, int32_t bucket, int32_t src_slot,
+                          float* residual_packed /* NULL: none */, int32_t k, void* slots,
+                          dl_stream_t stream);
+DL_API int dl_gather_topk_fp4(dl_tree_t tree, int32_t bucket, int32_t src_slot,
+                              float* residual_packed /* NULL: none */, int32_t k, void* slots,
+                              dl_stream_t stream);
+DL_API int dl_unpack_avg_topk(dl_tree_t tree, int32_t bucket, const void* slots, int32_t k,
+                              int32_t dst_slot, double* partials /* NULL: none */,
+                              dl_stream_t stream);
+DL_API int dl_unpack_avg_topk_fp4(dl_tree_t tree, int32_t bucket, const void* slots, int32_t k,
+                                  int32_t dst_slot, double* partials /* NULL: none */,
+                                  dl_stream_t stream);
+
 /* ---- serializer (src/serializer.py:11-15) ----------------------------------------------
  * out is fp32 of 2*numel elements: out[0] = meta0, out[1] = meta1, out[numel + i] =
  * float(src[i]) for src dtype DL_F32/DL_BF16/DL_F16. out[2..numel) is left unwritten, as
