@@ -1495,6 +1495,55 @@ DL_TOPK_GRAD_ENTRY_POINTS()
 DL_TOPK_GRAD_ENTRY_POINTS(_fp4)
 #undef DL_TOPK_GRAD_ENTRY_POINTS
 
+// The all-gather exchange of the top-k wires (dl_topk_ag.hip): dl_unpack_avg_topk's checks and
+// policies, after the checks of k and of where the peers' slots lie.
+}  // extern "C"
+
+namespace {
+
+int unpack_avg_topk_ag(const char* who, decltype(&dl::launch_unpack_avg_topk_ag) launch,
+                       dl_tree_t t, int32_t b, const void* gathered, int32_t n_peers,
+                       int32_t peer_stride, int32_t k, int32_t dst_slot, double* partials,
+                       dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_topk_k(k, who));
+  DL_TRY(check_packed(gathered, who, "gathered"));
+  if (partials) DL_TRY(check_partials(partials, who));
+  DL_TRY(make_launch(t, b, s, &L, who, kAutoNT, Big::two_chunks));
+  if (n_peers < 1) return fail(DL_E_ARG, "%s: n_peers %d", who, n_peers);
+  if (peer_stride < L.c1 - L.c0)
+    return fail(DL_E_ARG, "%s: peer_stride %d below the launch's %d chunks", who, peer_stride,
+                L.c1 - L.c0);
+  DL_TRY(check_slot(t, dst_slot, who));
+  DL_TRY(slot_begin(t, dst_slot, L.stream, who));
+  hipError_t e = launch(L, static_cast<const uint8_t*>(gathered), n_peers, peer_stride, k,
+                        dst_slot, partials);
+  return e == hipSuccess ? slot_end(t, dst_slot, L.stream, who) : hip_fail(e, who);
+}
+
+}  // namespace
+
+extern "C" {
+
+DL_API int dl_unpack_avg_topk_ag(dl_tree_t t, int32_t b, const void* gathered, int32_t n_peers,
+                                 int32_t peer_stride, int32_t k, int32_t dst_slot,
+                                 double* partials, dl_stream_t s) {
+  return unpack_avg_topk_ag("dl_unpack_avg_topk_ag", dl::launch_unpack_avg_topk_ag, t, b, gathered,
+                            n_peers, peer_stride, k, dst_slot, partials, s);
+}
+
+DL_API int dl_unpack_avg_topk_fp4_ag(dl_tree_t t, int32_t b, const void* gathered, int32_t n_peers,
+                                     int32_t peer_stride, int32_t k, int32_t dst_slot,
+                                     double* partials, dl_stream_t s) {
+  return unpack_avg_topk_ag("dl_unpack_avg_topk_fp4_ag", dl::launch_unpack_avg_topk_fp4_ag, t, b,
+                            gathered, n_peers, peer_stride, k, dst_slot, partials, s);
+}
+
+#ifdef DL_TUNING
+// measurement only (tools/topk_ag_bench.py): 1 = the wave-owned-quarters front end, 0 = the product's
+DL_API void dl_tune_topk_ag_form(int32_t waves) { dl::set_topk_ag_form(waves); }
+#endif
+
 DL_API int dl_norm_finish(const double* partials, int32_t n_partials, float max_norm, float* out2,
                           dl_stream_t s) {
   if (n_partials < 0) return fail(DL_E_ARG, "dl_norm_finish: n_partials %d", n_partials);

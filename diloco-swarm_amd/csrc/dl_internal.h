@@ -168,6 +168,16 @@ hipError_t launch_unpack_avg_topk(const Launch& L, const uint8_t* slots, int k, 
                                   double* partials);
 hipError_t launch_unpack_avg_topk_fp4(const Launch& L, const uint8_t* slots, int k, int dst_slot,
                                       double* partials);
+// the all-gather exchange of the top-k wires (dl_topk_ag.hip): gathered = [peer][slot], the slot
+// of chunk c from peer r at (r * peer_stride + c - L.c0) slots; g = (Σ_r decode_r) / n_peers (the
+// caller checked k, n_peers, peer_stride)
+hipError_t launch_unpack_avg_topk_ag(const Launch& L, const uint8_t* gathered, int n_peers,
+                                     int peer_stride, int k, int dst_slot, double* partials);
+hipError_t launch_unpack_avg_topk_fp4_ag(const Launch& L, const uint8_t* gathered, int n_peers,
+                                         int peer_stride, int k, int dst_slot, double* partials);
+#ifdef DL_TUNING
+void set_topk_ag_form(int waves);  // the wave-owned-quarters front end instead (measurement)
+#endif
 hipError_t launch_unpack_adamw(const Launch& L, const void* wire, int wire_dtype, int divisor,
                                float* outer, float* m1, float* m2, AdamArgs a, int inner_slot);
 hipError_t launch_delta_pack_adamw(const Launch& L, int inner_slot, float* outer, void* wire,

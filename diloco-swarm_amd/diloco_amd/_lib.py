@@ -189,6 +189,10 @@ SIGNATURES = {
     "dl_gather_topk_fp4": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "dl_unpack_avg_topk": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "dl_unpack_avg_topk_fp4": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    # the all-gather exchange of the top-k wires: (gathered, n_peers, peer_stride, k) in the
+    # place of (slots, k)
+    "dl_unpack_avg_topk_ag": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "dl_unpack_avg_topk_fp4_ag": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_gather": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, _vp]),
     "dl_scatter": (ctypes.c_int, [_vp, _i32, _vp, _i32, _vp]),
     "dl_serialize": (ctypes.c_int, [_vp, _i32, _i64, _f32, _f32, _vp, _vp]),

@@ -173,6 +173,10 @@ DP_FP4_EF = os.environ.get("DILOCO_DP_FP4_EF", "0").strip().lower() in _ON
 DP_TOPK = int(os.environ.get("DILOCO_DP_TOPK") or 64)
 DP_TOPK_VALUES = os.environ.get("DILOCO_DP_TOPK_VALUES") or "f32"
 DP_TOPK_EF = os.environ.get("DILOCO_DP_TOPK_EF", "1").strip().lower() in _ON
+# how the topk wire's slots travel (DILOCO_DP_TOPK_EXCHANGE): "reduce", the slot wires' all_to_all
+# -> reduce (selects again) -> all_gather, or "gather": one all_gather of every peer's slots,
+# summed in rank order by the decoder -- n-1 against 2(n-1)/n slots per chunk on the bus
+DP_TOPK_EXCHANGE = os.environ.get("DILOCO_DP_TOPK_EXCHANGE") or "reduce"
 
 
 def dp_wire():
@@ -189,7 +193,10 @@ def dp_topk() -> dict:
     nothing on any other (GradSync rejects them there)."""
     if DP_WIRE != "topk":
         return {}
-    return {"topk": int(DP_TOPK), "topk_values": DP_TOPK_VALUES}
+    kw = {"topk": int(DP_TOPK), "topk_values": DP_TOPK_VALUES}
+    if DP_TOPK_EXCHANGE != "reduce":  # the default passes nothing, as before the knob
+        kw["topk_exchange"] = DP_TOPK_EXCHANGE
+    return kw
 
 
 class DPSync:

@@ -76,6 +76,9 @@ from .plan import DEFAULT_BUCKET_CAP_ELEMS, SLOT_GRAD, q8_slot_plan
 SLOT_WIRES = {torch.int8: Q8_SLOT, "fp4": FP4_SLOT}
 
 
+TOPK_EXCHANGES = ("reduce", "gather")  # the top-k wire's exchange (GradSync's topk_exchange)
+
+
 def slot_wire_bytes(wire_dtype, topk: Optional[int] = None, topk_values: str = "f32"):
     """Bytes of one chunk's slot on `wire_dtype`; None on the flat wires (f32, bf16)."""
     if wire_dtype == "topk":
@@ -88,7 +91,8 @@ class GradSync:
                  world_size: int, wire_dtype=torch.float32,
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, kernels=None,
                  exchange: str = "rccl", error_feedback: Optional[bool] = None,
-                 topk: Optional[int] = None, topk_values: Optional[str] = None):
+                 topk: Optional[int] = None, topk_values: Optional[str] = None,
+                 topk_exchange: Optional[str] = None):
         self.params = list(params)
         self.k = kernels or default_kernels()
         self.device = self.params[0].device
@@ -117,6 +121,18 @@ class GradSync:
                              f"the wire is {wire_dtype!r}")
         if topk_values not in TOPK_VALUES:
             raise ValueError(f"topk_values {topk_values!r}: one of {TOPK_VALUES}")
+        if topk_exchange is None:
+            topk_exchange = "reduce"
+        elif not self.topk_wire:
+            raise ValueError(f"topk_exchange={topk_exchange!r} is how the 'topk' wire's slots "
+                             f"travel; the wire is {wire_dtype!r}")
+        if topk_exchange not in TOPK_EXCHANGES:
+            raise ValueError(f"topk_exchange {topk_exchange!r}: one of {TOPK_EXCHANGES}")
+        # "gather": every peer's slots to every peer in one all_gather, summed in rank order by the
+        # decoder (dl_unpack_avg_topk[_fp4]_ag) -- nothing is selected a second time, so error
+        # feedback is the encoder's residual alone; (n-1) · S bus bytes per chunk against
+        # 2(n-1)/n · S of "reduce" (the same at two peers)
+        self.topk_gather = self.topk_wire and topk_exchange == "gather"
         # the top-k wire only: entries per chunk, and "f32" or "fp4" values
         self.topk = int(topk) if self.topk_wire else None
         self.topk_values = topk_values if self.topk_wire else None
@@ -175,7 +191,11 @@ class GradSync:
         z = dict(dtype=torch.uint8, device=self.device)
         self.q_slots = torch.zeros(total * S, **z)
         self.q_recv = self.q_red = None
-        if not self.local:
+        if not self.local and self.topk_gather:
+            # the gathered slots, [peer][chunk of the bucket], for two buckets in flight
+            cmax = max((nch for nch, _m, _at, _rat in self.q8_plan), default=0)
+            self.q_recv = [torch.zeros(n * cmax * S, **z) for _ in range(2)]
+        elif not self.local:
             self.q_recv = [torch.zeros(n * mmax * S, **z) for _ in range(2)]
             self.q_red = [torch.zeros(mmax * S, **z) for _ in range(2)]
         # error feedback: the encoder's residual in the packed layout, and at n > 1 the
@@ -184,7 +204,7 @@ class GradSync:
         if self.error_feedback:
             f = dict(dtype=torch.float32, device=self.device)
             self.q_residual = torch.zeros(self.tree.total, **f)
-            if n > 1:
+            if n > 1 and not self.topk_gather:
                 self.q_residual_red = [torch.zeros(m * _lib.CHUNK_ELEMS, **f)
                                        for _nch, m, _at, _rat in self.q8_plan]
 
@@ -373,6 +393,9 @@ class GradSync:
         n, nb, S = self.world_size, self.tree.n_buckets, self.slot_bytes
         partials = None if clip is None else self.partials
         encode, reduce, decode = self._codec()
+        if self.topk_gather:
+            self._sync_gathered(encode, partials)
+            return
 
         if self.local:
             # one replica: the average of one is its own re-quantised slots (error feedback:
@@ -410,6 +433,41 @@ class GradSync:
                 decode(b - 1, partials)
         ag[nb - 1].wait()
         decode(nb - 1, partials)
+
+    def _sync_gathered(self, encode, partials) -> None:
+        """encode(b) -> all_gather(b) | sum, / n and decode(b) in one pass over the n peers' slots
+        (dl_unpack_avg_topk[_fp4]_ag), overlapped across buckets with alternating landing
+        buffers as _sync_slots. One replica: the decoder on the bucket's own slots, n_peers 1."""
+        n, nb, S, kk = self.world_size, self.tree.n_buckets, self.slot_bytes, self.topk
+        fp4 = self.topk_values == "fp4"
+
+        def decode(b, gathered, peers):
+            self.k.unpack_avg_topk_ag(self.tree, b, gathered, peers, self.q8_plan[b][0], kk,
+                                      SLOT_GRAD, partials, fp4=fp4)
+
+        if self.local:
+            for b in range(nb):
+                encode(b)
+                decode(b, self.q8_region(b), 1)
+            return
+
+        def landing(b):
+            return self.q_recv[b % 2][:n * self.q8_plan[b][0] * S]
+
+        def gather(b):
+            encode(b)
+            return dist.all_gather_into_tensor(landing(b), self.q8_region(b)[:self.q8_plan[b][0] * S],
+                                               group=self.group, async_op=True)
+
+        if nb == 0:
+            return
+        x = [None] * nb
+        x[0] = gather(0)
+        for b in range(nb):
+            if b + 1 < nb:
+                x[b + 1] = gather(b + 1)
+            x[b].wait()
+            decode(b, landing(b), n)
 
     def close(self) -> None:
         self.tree.close()

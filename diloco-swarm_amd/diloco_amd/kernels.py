@@ -411,6 +411,17 @@ class HipKernels:
         _lib.call("dl_unpack_avg_topk_fp4", tree.handle, bucket, slots.data_ptr(), int(k),
                   int(dst_slot), _ptr(partials), _s(slots))
 
+    # the all-gather exchange of the top-k wires (dl_topk_ag.hip): gathered = the landing buffer
+    # of an all_gather_into_tensor, [peer][slot], the slot of the launch's j-th chunk from peer r
+    # at (r * peer_stride + j) slots
+    def unpack_avg_topk_ag(self, tree, bucket, gathered, n_peers, peer_stride, k, dst_slot,
+                           partials=None, fp4=False) -> None:
+        """dst_slot <- (Σ_r decode_r in rank order) / n_peers; with partials also the per-chunk Σ
+        of the stored values². fp4: the (16 + 2k)-byte slots."""
+        _lib.call(f"dl_unpack_avg_topk{'_fp4' if fp4 else ''}_ag", tree.handle, bucket,
+                  gathered.data_ptr(), int(n_peers), int(peer_stride), int(k), int(dst_slot),
+                  _ptr(partials), _s(gathered))
+
     def unpack_avg(self, tree, bucket, wire, divisor, dst_slot, dst_packed=None) -> None:
         _lib.call("dl_unpack_avg", tree.handle, bucket, wire.data_ptr(), wire_code(wire.dtype),
                   int(divisor), int(dst_slot), _ptr(dst_packed), _s(wire))

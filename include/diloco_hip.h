@@ -803,6 +803,36 @@ DL_API int dl_unpack_avg_topk_fp4(dl_tree_t tree, int32_t bucket, const void* sl
                                   int32_t dst_slot, double* partials /* NULL: none */,
                                   dl_stream_t stream);
 
+/* ---- the all-gather exchange of the two top-k wires (not in the reference) ------------------
+ * The per-step DP gradient average on the top-k slots by one collective. Every peer receives every peer's slots (one all_gather_into_tensor) and sums them itself: no
+ * reduce call, no second selection, no second residual. The encoders are the ones above.
+ * gathered is that collective's landing buffer, laid out [peer][slot]: the slot of chunk c from
+ * peer r is at gathered + (r * peer_stride + (c - c0)) * S, c0 the launch's first chunk (the
+ * bucket's, or 0 for DL_ALL_BUCKETS), S = DL_TOPK_SLOT_BYTES(k) or DL_TOPK_FP4_SLOT_BYTES(k) for
+ * the _fp4 forms, peer_stride in slots and at least the launch's chunk count (the bucket's chunk
+ * count for a bucket launch, n_chunk for the whole tree; no padding slots). Per chunk:
+ *   acc = +0 over the chunk
+ *   for r = 0 .. n_peers - 1 in that order, every entry (value, index) of peer r's slot:
+ *     acc[index] = acc[index] + value     (one rounded fp32 add; _fp4: value = nibble x scale,
+ *                                          exact, decoded before the add)
+ *   g = acc / float(n_peers)              (IEEE division; n_peers 1: untouched)
+ * Indices are distinct within a valid slot (the all-zero slot: k entries (+0, 0)) and are taken
+ * modulo DL_CHUNK_ELEMS; for a slot that repeats an index otherwise the values at the repeated
+ * index are unspecified, and nothing is read or written outside the buffers named here.
+ * dl_unpack_avg_topk_ag / dl_unpack_avg_topk_fp4_ag, per chunk c of the bucket, dst = slot
+ * dst_slot (per-tensor fp32): dst[seg][i] = g for every element inside the chunk, the zeros too;
+ * partials as dl_unpack_avg_topk. gathered is only read; nothing is stored past a tensor's
+ * length. Results do not depend on alignment, the grid or the bucket split. k as above; n_peers
+ * < 1 or peer_stride below the launch's chunk count is DL_E_ARG. gathered non-null and 16-B
+ * aligned, partials 8-B aligned; the slot bound. */
+DL_API int dl_unpack_avg_topk_ag(dl_tree_t tree, int32_t bucket, const void* gathered,
+                                 int32_t n_peers, int32_t peer_stride, int32_t k, int32_t dst_slot,
+                                 double* partials /* NULL: none */, dl_stream_t stream);
+DL_API int dl_unpack_avg_topk_fp4_ag(dl_tree_t tree, int32_t bucket, const void* gathered,
+                                     int32_t n_peers, int32_t peer_stride, int32_t k,
+                                     int32_t dst_slot, double* partials /* NULL: none */,
+                                     dl_stream_t stream);
+
 /* ---- serializer (src/serializer.py:11-15) ----------------------------------------------
  * out is fp32 of 2*numel elements: out[0] = meta0, out[1] = meta1, out[numel + i] =
  * float(src[i]) for src dtype DL_F32/DL_BF16/DL_F16. out[2..numel) is left unwritten, as
