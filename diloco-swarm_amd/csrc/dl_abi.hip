@@ -1521,9 +1521,86 @@ int unpack_avg_topk_ag(const char* who, decltype(&dl::launch_unpack_avg_topk_ag)
   return e == hipSuccess ? slot_end(t, dst_slot, L.stream, who) : hip_fail(e, who);
 }
 
+// The outer step on the gathered slots (dl_topk_ag_outer.hip): the checks and policy of
+// unpack_sgd_topk / unpack_adamw_topk, with those of where the peers' slots lie in the place of
+// the check of `slots`.
+int check_topk_ag_src(const char* who, const dl::Launch& L, const void* gathered, int32_t n_peers,
+                      int32_t peer_stride) {
+  DL_TRY(check_packed(gathered, who, "gathered"));
+  if (n_peers < 1) return fail(DL_E_ARG, "%s: n_peers %d", who, n_peers);
+  if (peer_stride < L.c1 - L.c0)
+    return fail(DL_E_ARG, "%s: peer_stride %d below the launch's %d chunks", who, peer_stride,
+                L.c1 - L.c0);
+  return DL_OK;
+}
+
+int unpack_sgd_topk_ag(const char* who, decltype(&dl::launch_unpack_sgd_topk_ag) launch,
+                       dl_tree_t t, int32_t b, const void* gathered, int32_t n_peers,
+                       int32_t peer_stride, int32_t k, float* outer, float* mom, float lr,
+                       float momentum, int32_t nesterov, int32_t first_step, int32_t inner_slot,
+                       dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_topk_k(k, who));
+  DL_TRY(make_launch(t, b, s, &L, who, kAutoNT));
+  DL_TRY(check_topk_ag_src(who, L, gathered, n_peers, peer_stride));
+  DL_TRY(check_packed(outer, who, "outer"));
+  dl::SgdArgs a;
+  DL_TRY(sgd_args(who, mom, lr, momentum, nesterov, first_step, &a));
+  DL_TRY(check_slot(t, inner_slot, who, true));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, who));
+  hipError_t e = launch(L, static_cast<const uint8_t*>(gathered), n_peers, peer_stride, k, outer,
+                        mom, a, inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, who) : hip_fail(e, who);
+}
+
+int unpack_adamw_topk_ag(const char* who, decltype(&dl::launch_unpack_adamw_topk_ag) launch,
+                         dl_tree_t t, int32_t b, const void* gathered, int32_t n_peers,
+                         int32_t peer_stride, int32_t k, float* outer, float* exp_avg,
+                         float* exp_avg_sq, dl::AdamArgs a, int32_t inner_slot, dl_stream_t s) {
+  dl::Launch L;
+  DL_TRY(check_topk_k(k, who));
+  DL_TRY(make_launch(t, b, s, &L, who, kAutoNT));
+  DL_TRY(check_topk_ag_src(who, L, gathered, n_peers, peer_stride));
+  DL_TRY(check_packed(outer, who, "outer"));
+  DL_TRY(check_packed(exp_avg, who, "exp_avg"));
+  DL_TRY(check_packed(exp_avg_sq, who, "exp_avg_sq"));
+  DL_TRY(check_slot(t, inner_slot, who, true));
+  DL_TRY(slot_begin(t, inner_slot, L.stream, who));
+  hipError_t e = launch(L, static_cast<const uint8_t*>(gathered), n_peers, peer_stride, k, outer,
+                        exp_avg, exp_avg_sq, a, inner_slot);
+  return e == hipSuccess ? slot_end(t, inner_slot, L.stream, who) : hip_fail(e, who);
+}
+
 }  // namespace
 
 extern "C" {
+
+#define DL_TOPK_AG_OUTER_ENTRY_POINTS(SFX)                                                         \
+  DL_API int dl_unpack_sgd_topk##SFX##_ag(dl_tree_t t, int32_t b, const void* gathered,            \
+                                          int32_t n_peers, int32_t peer_stride, int32_t k,         \
+                                          float* outer, float* mom, float lr, float momentum,      \
+                                          int32_t nesterov, int32_t first_step,                    \
+                                          int32_t inner_slot, dl_stream_t s) {                     \
+    return unpack_sgd_topk_ag("dl_unpack_sgd_topk" #SFX "_ag",                                     \
+                              dl::launch_unpack_sgd_topk##SFX##_ag, t, b, gathered, n_peers,       \
+                              peer_stride, k, outer, mom, lr, momentum, nesterov, first_step,      \
+                              inner_slot, s);                                                      \
+  }                                                                                                \
+  DL_API int dl_unpack_adamw_topk##SFX##_ag(dl_tree_t t, int32_t b, const void* gathered,          \
+                                            int32_t n_peers, int32_t peer_stride, int32_t k,       \
+                                            float* outer, float* exp_avg, float* exp_avg_sq,       \
+                                            float decay, float w1, float beta2, float w2,          \
+                                            float neg_step_size, float bc2_sqrt, float eps,        \
+                                            int32_t inner_slot, dl_stream_t s) {                   \
+    return unpack_adamw_topk_ag("dl_unpack_adamw_topk" #SFX "_ag",                                 \
+                                dl::launch_unpack_adamw_topk##SFX##_ag, t, b, gathered, n_peers,   \
+                                peer_stride, k, outer, exp_avg, exp_avg_sq,                        \
+                                dl::AdamArgs{decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps},  \
+                                inner_slot, s);                                                    \
+  }
+DL_TOPK_AG_OUTER_ENTRY_POINTS()
+DL_TOPK_AG_OUTER_ENTRY_POINTS(_fp4)
+#undef DL_TOPK_AG_OUTER_ENTRY_POINTS
 
 DL_API int dl_unpack_avg_topk_ag(dl_tree_t t, int32_t b, const void* gathered, int32_t n_peers,
                                  int32_t peer_stride, int32_t k, int32_t dst_slot,
@@ -1540,7 +1617,9 @@ DL_API int dl_unpack_avg_topk_fp4_ag(dl_tree_t t, int32_t b, const void* gathere
 }
 
 #ifdef DL_TUNING
-// measurement only (tools/topk_ag_bench.py): 1 = the wave-owned-quarters front end, 0 = the product's
+// measurement only (tools/topk_ag_bench.py, tools/topk_ag_outer_bench.py): 1 = the
+// wave-owned-quarters front end (the product's in the outer step), 0 = the per-peer barriers (the
+// product's in the gradient decoder)
 DL_API void dl_tune_topk_ag_form(int32_t waves) { dl::set_topk_ag_form(waves); }
 #endif
 

@@ -175,8 +175,23 @@ hipError_t launch_unpack_avg_topk_ag(const Launch& L, const uint8_t* gathered, i
                                      int peer_stride, int k, int dst_slot, double* partials);
 hipError_t launch_unpack_avg_topk_fp4_ag(const Launch& L, const uint8_t* gathered, int n_peers,
                                          int peer_stride, int k, int dst_slot, double* partials);
+// the outer step on the gathered slots (dl_topk_ag_outer.hip): the same source, then the rule of
+// launch_unpack_sgd_topk / launch_unpack_adamw_topk on g and inner = θ
+hipError_t launch_unpack_sgd_topk_ag(const Launch& L, const uint8_t* gathered, int n_peers,
+                                     int peer_stride, int k, float* outer, float* mom, SgdArgs a,
+                                     int inner_slot);
+hipError_t launch_unpack_sgd_topk_fp4_ag(const Launch& L, const uint8_t* gathered, int n_peers,
+                                         int peer_stride, int k, float* outer, float* mom,
+                                         SgdArgs a, int inner_slot);
+hipError_t launch_unpack_adamw_topk_ag(const Launch& L, const uint8_t* gathered, int n_peers,
+                                       int peer_stride, int k, float* outer, float* m1, float* m2,
+                                       AdamArgs a, int inner_slot);
+hipError_t launch_unpack_adamw_topk_fp4_ag(const Launch& L, const uint8_t* gathered, int n_peers,
+                                           int peer_stride, int k, float* outer, float* m1,
+                                           float* m2, AdamArgs a, int inner_slot);
 #ifdef DL_TUNING
-void set_topk_ag_form(int waves);  // the wave-owned-quarters front end instead (measurement)
+void set_topk_ag_form(int waves);  // wave-owned quarters (1) or per-peer barriers (0), measurement
+bool topk_ag_form_waves();         // what it was last set to, for dl_topk_ag_outer.hip
 #endif
 hipError_t launch_unpack_adamw(const Launch& L, const void* wire, int wire_dtype, int divisor,
                                float* outer, float* m1, float* m2, AdamArgs a, int inner_slot);

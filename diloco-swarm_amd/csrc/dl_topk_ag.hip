@@ -93,6 +93,7 @@ hipError_t unpack_avg_ag(const Launch& L, const uint8_t* gathered, int n_peers, 
 
 #ifdef DL_TUNING
 void set_topk_ag_form(int waves) { g_ag_waves = waves != 0; }
+bool topk_ag_form_waves() { return g_ag_waves; }
 #endif
 
 hipError_t launch_unpack_avg_topk_ag(const Launch& L, const uint8_t* gathered, int n_peers,

@@ -10,20 +10,26 @@
 // bits. A slot that repeats a position otherwise is not a valid slot: which of the colliding adds
 // lands is unspecified, and nothing leaves the dense chunk.
 //
-// Two forms were measured in the write-only gradient decoder (tools/topk_ag_bench.py,
-// profiles/topk_ag_t125.json):
-//   TopkAgBarriers  the product's. One lane per entry, one workgroup barrier per peer, the next
+// Two forms, each measured in both kernels that use them: the write-only gradient decoder of
+// dl_topk_ag.hip (tools/topk_ag_bench.py, profiles/topk_ag_t125.json) and the outer step of
+// dl_topk_ag_outer.hip (tools/topk_ag_outer_bench.py, profiles/topk_ag_outer_t125.json). The
+// product library holds one form per kernel, the tuning build both (dl_tune_topk_ag_form).
+//   TopkAgBarriers  the gradient decoder's. One lane per entry, one workgroup barrier per peer, the next
 //                   peer's entry loaded ahead of the add: dl_topk_reduce's accumulate loop.
 //                   n + 1 barriers per chunk, one entry load per lane and peer.
-//   TopkAgWaves     tuning build only. No barrier between peers: the dense chunk is cut into
+//   TopkAgWaves     the outer step's. No barrier between peers: the dense chunk is cut into
 //                   kWaves quarters of 1024 positions and wave w alone zeroes, reads and writes
 //                   quarter w; every wave walks every peer's k entries itself (k/64 <= 4 per
 //                   lane) and adds only those whose position lies in its quarter, whatever their
 //                   order in the slot; peers stay ordered by the wave's program order (LDS
 //                   operations of one wave complete in issue order), and one barrier at the end
 //                   publishes the quarters. kWaves times the entry loads, and up to eight entries
-//                   in a lane's registers. It was 10 us slower at n = 2 and at n = 8: with nothing
-//                   else in flight the decoder waits on the entry loads, not on the barriers.
+//                   in a lane's registers. In the gradient decoder it was 10 us slower at n = 2
+//                   and at n = 8: with nothing else in flight that kernel waits on the entry
+//                   loads, not on the barriers. In the outer step the dense rows of θ and the
+//                   state are in flight behind the entry loads and every barrier holds all four
+//                   waves until the slowest has its entries: there it is level at n = 2 and 12 us
+//                   faster for SGD at n = 8, at the same occupancy.
 #pragma once
 #include "dl_topk_fp4_dev.h"
 
@@ -72,7 +78,6 @@ struct TopkAgBarriers {
   }
 };
 
-#ifdef DL_TUNING
 constexpr int kAgQuarter = DL_CHUNK_ELEMS / kWaves;  // positions a wave owns
 constexpr int kAgPerLane = DL_TOPK_MAX_K / 64;        // entries of one slot a lane walks at most
 static_assert(kAgQuarter % (4 * 64) == 0, "a wave zeroes its quarter in float4 rows");
@@ -125,7 +130,6 @@ struct TopkAgWaves {
     __syncthreads();
   }
 };
-#endif
 
 }  // namespace
 }  // namespace dl

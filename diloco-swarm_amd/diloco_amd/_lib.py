@@ -193,6 +193,25 @@ SIGNATURES = {
     # place of (slots, k)
     "dl_unpack_avg_topk_ag": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_unpack_avg_topk_fp4_ag": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    # the outer step on the gathered slots: the same replacement in dl_unpack_{sgd,adamw}_topk
+    "dl_unpack_sgd_topk_ag": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
+    ),
+    "dl_unpack_sgd_topk_fp4_ag": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp],
+    ),
+    "dl_unpack_adamw_topk_ag": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32,
+         _f32, _i32, _vp],
+    ),
+    "dl_unpack_adamw_topk_fp4_ag": (
+        ctypes.c_int,
+        [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32,
+         _f32, _i32, _vp],
+    ),
     "dl_gather": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, _vp]),
     "dl_scatter": (ctypes.c_int, [_vp, _i32, _vp, _i32, _vp]),
     "dl_serialize": (ctypes.c_int, [_vp, _i32, _i64, _f32, _f32, _vp, _vp]),

@@ -422,6 +422,21 @@ class HipKernels:
                   gathered.data_ptr(), int(n_peers), int(peer_stride), int(k), int(dst_slot),
                   _ptr(partials), _s(gathered))
 
+    # the outer step on the gathered slots (dl_topk_ag_outer.hip): unpack_sgd_topk /
+    # unpack_adamw_topk with g = (Σ_r decode_r in rank order) / n_peers
+    def unpack_sgd_topk_ag(self, tree, bucket, gathered, n_peers, peer_stride, k, theta, mom, lr,
+                           momentum, nesterov, first, inner_slot, fp4=False) -> None:
+        _lib.call(f"dl_unpack_sgd_topk{'_fp4' if fp4 else ''}_ag", tree.handle, bucket,
+                  gathered.data_ptr(), int(n_peers), int(peer_stride), int(k), theta.data_ptr(),
+                  _ptr(mom), float(lr), float(momentum), int(nesterov), int(first),
+                  int(inner_slot), _s(theta))
+
+    def unpack_adamw_topk_ag(self, tree, bucket, gathered, n_peers, peer_stride, k, theta, exp_avg,
+                             exp_avg_sq, scalars, inner_slot, fp4=False) -> None:
+        _lib.call(f"dl_unpack_adamw_topk{'_fp4' if fp4 else ''}_ag", tree.handle, bucket,
+                  gathered.data_ptr(), int(n_peers), int(peer_stride), int(k), theta.data_ptr(),
+                  exp_avg.data_ptr(), exp_avg_sq.data_ptr(), *scalars, int(inner_slot), _s(theta))
+
     def unpack_avg(self, tree, bucket, wire, divisor, dst_slot, dst_packed=None) -> None:
         _lib.call("dl_unpack_avg", tree.handle, bucket, wire.data_ptr(), wire_code(wire.dtype),
                   int(divisor), int(dst_slot), _ptr(dst_packed), _s(wire))

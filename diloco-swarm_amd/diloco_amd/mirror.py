@@ -117,6 +117,11 @@ DEFAULT_TOPK = 64  # entries per chunk of the "topk" wire (DILOCO_OUTER_TOPK)
 # in a 6k-byte slot (dl_topk.hip), or "fp4", an E2M1 nibble beside the 12-bit position in one
 # u16, a scale byte per 32 entries, 16 + 2k bytes (dl_topk_fp4.hip)
 TOPK_VALUES = ("f32", "fp4")
+# How the "topk" wire's slots meet (DILOCO_OUTER_TOPK_EXCHANGE): "reduce", all_to_all ->
+# dl_topk[_fp4]_reduce (selected again, a second residual) -> all_gather of the survivors; or
+# "gather", ONE all_gather_into_tensor of every peer's slots and the rank-ordered sum inside the
+# optimizer pass (dl_topk_ag_outer.hip): one selection, no reduce kernel, no stage-2 residual
+TOPK_EXCHANGES = ("reduce", "gather")
 # The fp4 wire's randomised Hadamard rotation (dl_fp4_rot.hip; DILOCO_OUTER_FP4_ROTATE, off if
 # unset): the seed of its signs (DILOCO_OUTER_FP4_SEED) must be the same on every rank -- a peer
 # that decodes with another seed reads noise.
@@ -718,7 +723,8 @@ class DeviceOuterMirror:
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = False,
                  wire: str = "f32", exchange: str = "sharded", keep_params: bool = False,
                  error_feedback: bool = False, topk: int = DEFAULT_TOPK, rotate: bool = False,
-                 rot_seed: int = DEFAULT_FP4_SEED, topk_values: str = "f32"):
+                 rot_seed: int = DEFAULT_FP4_SEED, topk_values: str = "f32",
+                 topk_exchange: str = "reduce"):
         """keep_params: the outer model's Parameter objects stay the ones it has (their class
         switched to OuterParameter in place) -- for an outer model that got its device only
         at its first compute_pseudo_gradient, after get_optimizer took references to them.
@@ -754,6 +760,13 @@ class DeviceOuterMirror:
         # the "topk" wire's kernel set: the _topk methods, or their _topk_fp4 twins
         self.topk_values = topk_values
         self._tk = "topk_fp4" if topk_values == "fp4" else "topk"
+        if topk_exchange not in TOPK_EXCHANGES:
+            raise ValueError(f"topk_exchange {topk_exchange!r}: one of {TOPK_EXCHANGES}")
+        if topk_exchange != "reduce" and wire != "topk":
+            raise ValueError(f"topk_exchange={topk_exchange!r} is how the 'topk' wire's slots "
+                             f"meet; the wire is {wire!r}")
+        # every peer's slots gathered and summed in the optimizer pass (_all_gather_topk)
+        self.topk_gather = topk_exchange == "gather"
         self._q8_res: Optional[torch.Tensor] = None
         self._q8_res_load: Optional[list] = None  # a loaded stage-2 state, until the buffers exist
         self.exchange = exchange
@@ -1410,8 +1423,20 @@ class DeviceOuterMirror:
         if self.wire == "topk":
             S = (_lib.TOPK_FP4_SLOT_BYTES if self.topk_values == "fp4"
                  else _lib.TOPK_SLOT_BYTES)(self.topk)
-        plan, base, rbase, mmax = q8_slot_plan(self.tree.bucket_chunks, n)
         z = dict(dtype=torch.uint8, device=self.device)
+        if self.topk_gather:
+            # this rank's slots in chunk order, and per bucket a gathered region of n·nch slots
+            # ([peer][slot], no padding) that persists until the next exchange: .grad may be
+            # read after the step. No landing pair, no reduced region, no stage-2 residual.
+            nch = self.tree.n_chunks
+            if self._q8_res_load:
+                raise ValueError("the int8 error-feedback state does not match this exchange's "
+                                 "buckets and peer count")
+            self._q8_res_load = None
+            self._q8 = q = {"n": n, "plan": [], "S": S, "slots": torch.zeros(nch * S, **z),
+                            "gath": torch.zeros(n * nch * S, **z)}
+            return q
+        plan, base, rbase, mmax = q8_slot_plan(self.tree.bucket_chunks, n)
         segs = []
         for lo, hi in self.tree.bucket_ranges:
             segs.append([i for i, o in enumerate(self.offs) if lo <= o < hi])
@@ -1466,7 +1491,7 @@ class DeviceOuterMirror:
         if state is None:
             if self._q8_res is not None:
                 self._q8_res.zero_()
-            if q is not None:
+            if q is not None and "res" in q:
                 q["res"].zero_()
             self._q8_res_load = None
             return
@@ -1475,6 +1500,9 @@ class DeviceOuterMirror:
             raise ValueError(f"int8 error-feedback state: encode residual of {tuple(enc.shape)}, "
                              f"expected ({self.tree.total},)")
         red = [a.to(**z) for a in state["reduce"]]
+        if self.topk_gather and red:  # the gathered exchange has no second residual
+            raise ValueError("the int8 error-feedback state does not match this exchange's "
+                             "buckets and peer count")
         if q is not None:
             self._q8_set_reduce_state(red)
         else:
@@ -1523,6 +1551,10 @@ class DeviceOuterMirror:
         if ef and self._q8_res is None:
             self._q8_res = torch.zeros(self.tree.total, dtype=torch.float32, device=self.device)
 
+        if self.topk_gather:
+            self._all_gather_topk(group, n, q, theta, slot)
+            return
+
         def pack(b):  # with error feedback both encode paths carry the residual
             self._slot_encode(b, slot, theta, self._q8_res if ef else None, self._q8_region(q, b))
 
@@ -1550,6 +1582,46 @@ class DeviceOuterMirror:
         if not self.fused:
             self._decode_q8()
 
+    # ---- the "topk" wire's gathered exchange (topk_exchange="gather") --------------------------
+    def _ag_send(self, q: dict, b: int) -> torch.Tensor:
+        c0, c1 = self.tree.bucket_chunks[b]
+        return q["slots"][c0 * q["S"]:c1 * q["S"]]
+
+    def _ag_region(self, q: dict, b: int) -> torch.Tensor:
+        c0, c1 = self.tree.bucket_chunks[b]
+        return q["gath"][q["n"] * c0 * q["S"]:q["n"] * c1 * q["S"]]
+
+    def _all_gather_topk(self, group, n: int, q: dict, theta, slot: int) -> None:
+        """Per bucket: dl_delta_topk[_fp4] as in the reduce path (this rank's residual with error
+        feedback) -> ONE all_gather_into_tensor of the bucket's nch slots into its gathered region
+        (peer_stride = nch), left in flight; the next bucket's encode is issued ahead of it.
+        Nothing is selected again: the optimizer passes (dl_unpack_*_topk[_fp4]_ag) and .grad's
+        decode (dl_unpack_avg_topk[_fp4]_ag) sum the n peers' slots in rank order themselves."""
+        nb = self.tree.n_buckets
+        res = self._q8_res if self.error_feedback else None
+        works = [None] * nb
+        self._slot_encode(0, slot, theta, res, self._ag_send(q, 0))
+        for b in range(nb):
+            if b + 1 < nb:
+                self._slot_encode(b + 1, slot, theta, res, self._ag_send(q, b + 1))
+            works[b] = dist.all_gather_into_tensor(self._ag_region(q, b), self._ag_send(q, b),
+                                                   group=group, async_op=True)
+        self._works = works
+        self._xmode, self._div = "q8", 1
+        if not self.fused:
+            self._decode_q8()
+
+    def _decode_topk_ag(self, q: dict) -> None:
+        """.grad's fp32 arena <- (Σ_r decode_r) / n of the gathered regions, by the gradient
+        sync's decoder on the arena's per-tensor views (bound to a tree slot of their own)."""
+        from .plan import SLOT_AUX2
+        self.k.bind(self.tree, SLOT_AUX2, self._views["wire"], self.device,
+                    key=tuple(self._ptrs["wire"]))
+        for b in range(self.tree.n_buckets):
+            c0, c1 = self.tree.bucket_chunks[b]
+            self.k.unpack_avg_topk_ag(self.tree, b, self._ag_region(q, b), q["n"], c1 - c0,
+                                      self.topk, SLOT_AUX2, fp4=self.topk_values == "fp4")
+
     def _decode_q8(self) -> None:
         """The averaged slots -> .grad's fp32 arena: g = q · s per chunk (the product
         dl_unpack_sgd_q8 forms in registers), chunk j of a tensor covering its elements
@@ -1557,6 +1629,9 @@ class DeviceOuterMirror:
         self._join()
         self._xmode = None
         q = self._q8
+        if self.topk_gather:
+            self._decode_topk_ag(q)
+            return
         S, C = q["S"], S_CHUNK
         for b in range(self.tree.n_buckets):
             nch, m, base, _ = q["plan"][b]
@@ -1590,6 +1665,13 @@ class DeviceOuterMirror:
         for b in range(self.tree.n_buckets):
             if works is not None:
                 works[b].wait()
+            if self.topk_gather:
+                c0, c1 = self.tree.bucket_chunks[b]
+                self.k.unpack_sgd_topk_ag(
+                    self.tree, b, self._ag_region(q, b), q["n"], c1 - c0, self.topk, self.d_theta,
+                    mom, lr, momentum, nesterov, first, SLOT_INNER if write else -1,
+                    fp4=self.topk_values == "fp4")
+                continue
             if self.wire == "topk":
                 getattr(self.k, "unpack_sgd_" + self._tk)(
                     self.tree, b, self._q8_region(q, b), self.topk, self.d_theta, mom, lr,
@@ -1617,6 +1699,13 @@ class DeviceOuterMirror:
         for b in range(self.tree.n_buckets):
             if works is not None:
                 works[b].wait()
+            if self.topk_gather:
+                c0, c1 = self.tree.bucket_chunks[b]
+                self.k.unpack_adamw_topk_ag(
+                    self.tree, b, self._ag_region(q, b), q["n"], c1 - c0, self.topk, self.d_theta,
+                    self.d_m1, self.d_m2, scalars, SLOT_INNER if write else -1,
+                    fp4=self.topk_values == "fp4")
+                continue
             if self.wire == "topk":
                 getattr(self.k, "unpack_adamw_" + self._tk)(
                     self.tree, b, self._q8_region(q, b), self.topk, self.d_theta, self.d_m1,
@@ -2053,7 +2142,8 @@ class LazyHostOuterMirror:
                  bucket_cap_elems: int = DEFAULT_BUCKET_CAP_ELEMS, fused: bool = True,
                  wire: str = "f32", exchange: str = DEFAULT_EXCHANGE["host"],
                  error_feedback: bool = False, topk: int = DEFAULT_TOPK, rotate: bool = False,
-                 rot_seed: int = DEFAULT_FP4_SEED, topk_values: str = "f32"):
+                 rot_seed: int = DEFAULT_FP4_SEED, topk_values: str = "f32",
+                 topk_exchange: str = "reduce"):
         self.device = torch.device(device)
         params = module_params(outer_model)
         if not params:
@@ -2066,7 +2156,8 @@ class LazyHostOuterMirror:
                 for p in params])
         self.dev = DeviceOuterMirror(twin, self.device, kernels, bucket_cap_elems, fused, wire,
                                      exchange, error_feedback=error_feedback, topk=topk,
-                                     rotate=rotate, rot_seed=rot_seed, topk_values=topk_values)
+                                     rotate=rotate, rot_seed=rot_seed, topk_values=topk_values,
+                                     topk_exchange=topk_exchange)
         self._twin = twin
         self.fused, self.wire, self.exchange = fused, wire, exchange
         from .utils import env_flag

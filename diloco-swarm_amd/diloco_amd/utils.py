@@ -82,7 +82,7 @@ from torch.optim import SGD, AdamW, Optimizer
 
 from .kernels import default_kernels
 from .mirror import (DEFAULT_EXCHANGE, DEFAULT_FP4_SEED, DEFAULT_TOPK, OUTER_EXCHANGES, OUTER_WIRES, SLOT_WIRES,
-                     TOPK_VALUES, WRITE_BACKS, DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
+                     TOPK_EXCHANGES, TOPK_VALUES, WRITE_BACKS, DeviceOuterMirror, HostOuterMirror, LazyHostOuterMirror, module_params)
 from .optim import InnerAdamW, OuterAdamW, OuterSGD
 from . import _lib
 from ._lib import ALL_BUCKETS
@@ -99,6 +99,7 @@ _EXCHANGE_ASKED = "_diloco_exchange_asked"  # by argument or DILOCO_OUTER_EXCHAN
 _Q8_EF = "_diloco_q8_ef"  # int8 wire with error feedback (DILOCO_OUTER_Q8_EF)
 _TOPK = "_diloco_topk"  # entries per chunk of the "topk" wire (DILOCO_OUTER_TOPK)
 _TOPK_VALUES = "_diloco_topk_values"  # "fp4": the "topk" wire's 4-bit values (DILOCO_OUTER_TOPK_VALUES)
+_TOPK_EXCHANGE = "_diloco_topk_exchange"  # "gather": one all_gather of the "topk" wire's slots (DILOCO_OUTER_TOPK_EXCHANGE)
 _ROTATE = "_diloco_fp4_rotate"  # the fp4 wire's rotation seed when it is on, else None
 _ADAMW = "_diloco_adamw"  # an optim.OuterAdamW is attached
 OUTER_ADAMW = ("torch", "fused")
@@ -166,6 +167,8 @@ def outer_mirror(outer_model: nn.Module, device=None):
             ef["topk"] = getattr(outer_model, _TOPK)
             if getattr(outer_model, _TOPK_VALUES, "f32") != "f32":  # likewise
                 ef["topk_values"] = getattr(outer_model, _TOPK_VALUES)
+            if getattr(outer_model, _TOPK_EXCHANGE, "reduce") != "reduce":  # likewise
+                ef["topk_exchange"] = getattr(outer_model, _TOPK_EXCHANGE)
         if getattr(outer_model, _ROTATE, None) is not None:  # likewise
             ef.update(rotate=True, rot_seed=getattr(outer_model, _ROTATE))
         if getattr(outer_model, _PLACEMENT, "host") == "device":
@@ -224,7 +227,8 @@ def _inner_device(inner_model: nn.Module) -> torch.device:
 def get_outer_model(inner_model: nn.Module, placement: str = None,
                     write_back: str = None, fused: bool = None, wire: str = None,
                     exchange: str = None, error_feedback: bool = None,
-                    topk: int = None, rotate: bool = None, topk_values: str = None) -> nn.Module:
+                    topk: int = None, rotate: bool = None, topk_values: str = None,
+                    topk_exchange: str = None) -> nn.Module:
     """Initializes the outer model from the inner model (src/utils.py:213-216).
 
     placement "host" (the reference's, default) or "device" (in HBM: on the inner model's GPU;
@@ -248,7 +252,13 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     reads DILOCO_OUTER_TOPK_VALUES, default "f32"): "fp4" sends each selected entry as one u16,
     its 12-bit position beside an E2M1 nibble under a scale byte per 32 entries (16 + 2k bytes
     per chunk instead of 6k; dl_delta_topk_fp4, dl_topk_fp4_reduce, dl_unpack_*_topk_fp4); the
-    selection is unchanged and the rounding error joins the residual. rotate (fp4 wire only; None reads
+    selection is unchanged and the rounding error joins the residual. topk_exchange (topk wire
+    only; None reads DILOCO_OUTER_TOPK_EXCHANGE, default "reduce", the path above): "gather" runs
+    ONE all_gather_into_tensor of every peer's slots per bucket and sums them in rank order inside
+    the optimizer pass (dl_unpack_sgd_topk_ag / dl_unpack_adamw_topk_ag and their _fp4 forms;
+    .grad through dl_unpack_avg_topk_ag): nothing is selected twice, there is no reduce kernel
+    and no stage-2 residual (q8_error_feedback_state(...)["reduce"] == []), at n times the
+    slot bytes received per rank. rotate (fp4 wire only; None reads
     DILOCO_OUTER_FP4_ROTATE, default off): every 256-element block is multiplied by random signs
     and Hadamard-transformed before the quantiser and transformed back after the decoder
     (dl_delta_fp4_rot, dl_unpack_*_fp4_rot, dl_decode_fp4_rot for .grad), which makes the
@@ -300,6 +310,14 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
                          f"wire is {wire!r}")
     if topk_values not in TOPK_VALUES:
         raise ValueError(f"topk_values {topk_values!r}: one of {TOPK_VALUES}")
+    if topk_exchange is None:  # consulted for its own wire only
+        topk_exchange = ((os.environ.get("DILOCO_OUTER_TOPK_EXCHANGE") or "reduce")
+                         if wire == "topk" else "reduce")
+    if topk_exchange not in TOPK_EXCHANGES:
+        raise ValueError(f"topk_exchange {topk_exchange!r}: one of {TOPK_EXCHANGES}")
+    if topk_exchange != "reduce" and wire != "topk":
+        raise ValueError(f"topk_exchange={topk_exchange!r} is how the 'topk' wire's slots meet; "
+                         f"the wire is {wire!r}")
     if exchange is None:
         exchange = os.environ.get("DILOCO_OUTER_EXCHANGE") or None
     asked = exchange is not None
@@ -336,6 +354,7 @@ def get_outer_model(inner_model: nn.Module, placement: str = None,
     object.__setattr__(outer_model, _Q8_EF, bool(error_feedback))
     object.__setattr__(outer_model, _TOPK, topk)
     object.__setattr__(outer_model, _TOPK_VALUES, topk_values)
+    object.__setattr__(outer_model, _TOPK_EXCHANGE, topk_exchange)
     object.__setattr__(outer_model, _ROTATE, seed)
     object.__setattr__(outer_model, _EXCHANGE, exchange)
     object.__setattr__(outer_model, _EXCHANGE_ASKED, asked)

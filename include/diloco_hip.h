@@ -832,6 +832,42 @@ DL_API int dl_unpack_avg_topk_fp4_ag(dl_tree_t tree, int32_t bucket, const void*
                                      int32_t n_peers, int32_t peer_stride, int32_t k,
                                      int32_t dst_slot, double* partials /* NULL: none */,
                                      dl_stream_t stream);
+/* The outer step on the gathered slots: dl_unpack_sgd_topk / dl_unpack_adamw_topk (and their
+ * _fp4 forms) with (gathered, n_peers, peer_stride) in the place of slots, so the outer exchange
+ * needs no dl_topk_reduce, no second selection and no stage-2 residual. Per chunk c of the
+ * bucket: g as above (acc = +0; peers in rank order, one rounded fp32 add per entry;
+ * / float(n_peers) by IEEE division when n_peers > 1), then one element of dl_unpack_sgd /
+ * dl_unpack_adamw at divisor 1 and inner[seg][i] = θ (inner_slot < 0: no inner write):
+ * bit-identical to dl_unpack_avg_topk_ag / dl_unpack_avg_topk_fp4_ag into an fp32 wire followed
+ * by dl_unpack_sgd / dl_unpack_adamw on it. Every element inside the chunk is stepped (a zero
+ * gradient still decays momentum); gathered is only read; nothing is stored past a chunk's or a
+ * tensor's length; results do not depend on the inner tensors' alignment, the grid or the bucket
+ * split. At k = 64: 20 + n_peers * 6k/4096 B/param for SGD, 28 + n_peers * 6k/4096 for AdamW,
+ * (16 + 2k)/4096 per peer for _fp4. The layout of gathered, k, n_peers and peer_stride and their
+ * checks are dl_unpack_avg_topk_ag's; gathered, outer and the state pointers 16-B aligned; every
+ * other argument and its check is dl_unpack_sgd_topk's / dl_unpack_adamw_topk's. */
+DL_API int dl_unpack_sgd_topk_ag(dl_tree_t tree, int32_t bucket, const void* gathered,
+                                 int32_t n_peers, int32_t peer_stride, int32_t k,
+                                 float* outer_packed, float* mom_packed, float lr, float momentum,
+                                 int32_t nesterov, int32_t first_step, int32_t inner_slot,
+                                 dl_stream_t stream);
+DL_API int dl_unpack_sgd_topk_fp4_ag(dl_tree_t tree, int32_t bucket, const void* gathered,
+                                     int32_t n_peers, int32_t peer_stride, int32_t k,
+                                     float* outer_packed, float* mom_packed, float lr,
+                                     float momentum, int32_t nesterov, int32_t first_step,
+                                     int32_t inner_slot, dl_stream_t stream);
+DL_API int dl_unpack_adamw_topk_ag(dl_tree_t tree, int32_t bucket, const void* gathered,
+                                   int32_t n_peers, int32_t peer_stride, int32_t k,
+                                   float* outer_packed, float* exp_avg_packed,
+                                   float* exp_avg_sq_packed, float decay, float w1, float beta2,
+                                   float w2, float neg_step_size, float bc2_sqrt, float eps,
+                                   int32_t inner_slot, dl_stream_t stream);
+DL_API int dl_unpack_adamw_topk_fp4_ag(dl_tree_t tree, int32_t bucket, const void* gathered,
+                                       int32_t n_peers, int32_t peer_stride, int32_t k,
+                                       float* outer_packed, float* exp_avg_packed,
+                                       float* exp_avg_sq_packed, float decay, float w1,
+                                       float beta2, float w2, float neg_step_size, float bc2_sqrt,
+                                       float eps, int32_t inner_slot, dl_stream_t stream);
 
 /* ---- serializer (src/serializer.py:11-15) ----------------------------------------------
  * out is fp32 of 2*numel elements: out[0] = meta0, out[1] = meta1, out[numel + i] =
